@@ -18,9 +18,14 @@ Workload (configs[1] of BASELINE.json): 32 utterances/GPU, 10 ODE steps, bf16 MF
 synthetic LJSpeech-shaped text (x_len ~ U[150,251] with blanks) and synthetic weights
 with the duration head forced to 3 frames/token -> 450..753 frames each.
 ``value`` = useful mel frames (sum of y_lengths) of all ranks / max-rank wall time.
-Sub-records on rank 0 at N=1 (default workload): ``north_star`` (B=256 on one GPU), ``general_attention``
-(a B=32 batch whose longest utterance is unpadded: the decoder's general attention path), ``batch1``
-(batch-1 RTF as the reference's notebook times it), ``fp32_parity_mode`` and ``cpu_baseline``.
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline of the kernels
+probed inside its last timed step). ``--dump-outputs DIR`` also writes what the last timed step returned (mel,
+y_lengths, wav) as ``DIR/<name>.npy``: the inputs and the noise depend only on the arguments, so two builds can be
+compared output for output.
+``--full`` adds the sub-records on rank 0 at N=1 (default workload), each a run of its own after the headline:
+``north_star`` (B=256 on one GPU), ``general_attention`` (a B=32 batch whose longest utterance is unpadded: the
+decoder's general attention path), ``batch1`` (batch-1 RTF as the reference's notebook times it),
+``fp32_parity_mode`` and ``cpu_baseline``.
 """
 from __future__ import annotations
 
@@ -55,6 +60,12 @@ def parse(argv=None):
     p.add_argument("--no-north-star", action="store_true", help="skip the B=256 single-GPU record")
     p.add_argument("--no-fp32", action="store_true", help="skip the fp32 parity-mode record")
     p.add_argument("--quick", action="store_true", help="headline line only: no sub-record, no CPU baseline")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run, also measure the sub-records (north_star, general_attention, batch1, "
+                        "fp32_parity_mode, cpu_baseline; the --no-* switches and --quick drop some of them). Without "
+                        "it the run sets up, warms up, times --steps steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (mel, y_lengths, wav) as DIR/<name>.npy")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--model", default="lj", choices=["lj", "vctk"],
                    help="lj: single speaker (configs[1..2]); vctk: 109 speakers with the speaker-embedding "
@@ -193,6 +204,30 @@ def step(m, g, den, x, xl, n_ts, denoise, spk=None):
     if denoise:
         wav = den(wav.squeeze(1), strength=0.00025, lengths=yl)
     return mel, yl, wav
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy payload per --dump-outputs directory
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """--dump-outputs: the tensors the last timed step returned, as ``path/<name><suffix>.npy`` (float32; integer
+    tensors as float64). The whole directory stays under DUMP_BUDGET bytes: the arrays are served smallest first, each
+    whole while it fits its even share of what is left, else as a fixed sample of its flattened elements (sorted
+    indices drawn by RandomState(0) from the element count, so the same positions in every run and every build)."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.to(torch.float32 if t.is_floating_point() else torch.float64).contiguous().numpy()
+    left = DUMP_BUDGET
+    for i, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).randint(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 # SURVEY.md §8d per-frame algorithmic cost of the hot path (one padded mel frame of one utterance):
@@ -565,15 +600,18 @@ def main(argv=None):
     rt.probe_start(rt.PROBE_VCONV, 64)
     rt.probe_pause(True)
     barrier()
+    last = None
     t0 = time.perf_counter()
     for i in range(a.steps):
         if i == a.steps - 1:
             rt.probe_pause(False)
-        step(m, g, den, x, xl, a.n_timesteps, denoise, spk)
+        last = step(m, g, den, x, xl, a.n_timesteps, denoise, spk)
     barrier()
     el = time.perf_counter() - t0
     detail = rt.probe_detail()
     probe = rt.probe_stop()
+    if a.dump_outputs and last is not None:
+        dump_outputs(a.dump_outputs, dict(zip(("mel", "y_lengths", "wav"), last)), f"_rank{rank}" if rank else "")
 
     el, tot_frames = reduce_over_ranks(el, frames, dist, device)
 
@@ -603,8 +641,8 @@ def main(argv=None):
             out["roofline"] = roofline(probe, default_workload=default, frame_scale=fs)
             out["roofline"]["by_kernel"] = roofline_by_kernel(detail, frame_scale=fs)
             out["path_roofline"] = path_roofline(el / a.steps, yls, t_pad, a.n_timesteps)
-            if a.quick:
-                a.no_north_star = a.no_cpu_baseline = a.no_fp32 = True
+            if a.quick or not a.full:
+                a.quick = a.no_north_star = a.no_cpu_baseline = a.no_fp32 = True
             if default and not a.quick:
                 out["general_attention"] = general_attention_record(m, g, den, a.batch, a.seed, a.n_timesteps,
                                                                     denoise)

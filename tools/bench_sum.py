@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-screen summary of a bench.py JSON line (the headline, north star, general attention, roofline by kernel).
+"""One-screen summary of a `bench.py --full` JSON line (the headline, north star, general attention, roofline by kernel).
 Usage: python tools/bench_sum.py gpurun_out/TAG/bench.log"""
 import json
 import sys

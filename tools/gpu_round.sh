@@ -9,5 +9,5 @@ rc=$?; echo "pytest rc=$rc"; grep -E "^(FAILED|ERROR)|passed|failed" $OUT/tests.
 [ $rc -le 1 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -5 $OUT/smoke.log; exit 1; }
 echo "smoke ok"
-timeout -k 10 400 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1; echo "bench rc=$?"
+timeout -k 10 400 python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1; echo "bench rc=$?"
 tail -c 1200 $OUT/bench.log

@@ -19,5 +19,6 @@ case $PART in
     bash tools/pmc.sh "${TAG}_pmc" "." -- python3 bench.py --quick --steps 1 --warmup 1 || exit 1
     python3 tools/pmc_table.py "gpurun_out/${TAG}_pmc" > "gpurun_out/${TAG}_pmc/pmc_kernels.txt" 2>&1; echo "pmc table rc=$?"
     rm -rf "gpurun_out/${TAG}_pmc"/p[0-9] ;;
-  bench) timeout -k 10 900 python -u bench.py > "gpurun_out/${TAG}_bench.log" 2>&1; echo "bench rc=$?"; tail -c 600 "gpurun_out/${TAG}_bench.log" ;;
+  bench) LOG="${OUT_ROOT:-bench_out}/${TAG}_bench.log"; mkdir -p "$(dirname "$LOG")"
+    timeout -k 10 900 python -u bench.py --full > "$LOG" 2>&1; echo "bench rc=$?"; tail -c 600 "$LOG" ;;
 esac
