@@ -303,6 +303,14 @@ int mtt_seq_mask(const int64_t* lengths, int B, int T, float* out, void* stream)
 size_t mtt_colsum_scratch_floats(int rows, int C, int seg);
 int mtt_colsum(const float* a, const float* b, int rows, int C, int seg, float* out, int accumulate, float* scratch,
                void* stream);
+/* dst[r][doff + j] = src[r / seg][j], r < rows, j < n: one vector per utterance repeated over its seg rows into a
+ * column slice of [rows][ldd] (spks.unsqueeze(-1).repeat + cat, model.py:528, 977-979). Writes only that slice. */
+int mtt_bcast_cols(const float* src, int n, float* dst, int ldd, int doff, int rows, int seg, void* stream);
+/* out[s][j] (+)= sum over the rows r of segment s (seg rows each) of a[r*lda + soff + j], j < n: the adjoint of
+ * mtt_bcast_cols, read in place from a column slice (no split copy). scratch >= mtt_segsum_cols_scratch_floats(). */
+size_t mtt_segsum_cols_scratch_floats(int rows, int n, int seg);
+int mtt_segsum_cols(const float* a, int lda, int soff, int n, int rows, int seg, float* out, int accumulate,
+                    float* scratch, void* stream);
 /* out[0] = sum_i a[i] (* b[i]); scratch >= 1024 floats */
 int mtt_sum(const float* a, const float* b, size_t n, float* out, float* scratch, void* stream);
 /* dropout(p) with a counter-based hash mask of (seed, index): out = a * keep / (1 - p); the backward is the same

@@ -489,6 +489,14 @@ int mtt_colsum(const float* a, const float* b, int rows, int C, int seg, float* 
                void* stream) {
   return mt::colsum(a, b, rows, C, seg, out, accumulate, scratch, (hipStream_t)stream);
 }
+int mtt_bcast_cols(const float* src, int n, float* dst, int ldd, int doff, int rows, int seg, void* stream) {
+  return mt::bcast_cols(src, n, dst, ldd, doff, rows, seg, (hipStream_t)stream);
+}
+size_t mtt_segsum_cols_scratch_floats(int rows, int n, int seg) { return mt::segsum_cols_scratch_floats(rows, n, seg); }
+int mtt_segsum_cols(const float* a, int lda, int soff, int n, int rows, int seg, float* out, int accumulate,
+                    float* scratch, void* stream) {
+  return mt::segsum_cols(a, lda, soff, n, rows, seg, out, accumulate, scratch, (hipStream_t)stream);
+}
 int mtt_sum(const float* a, const float* b, size_t n, float* out, float* scratch, void* stream) {
   return mt::sum_all(a, b, n, out, scratch, (hipStream_t)stream);
 }

@@ -69,6 +69,10 @@ int seq_mask(const long long* lengths, int B, int T, float* out, hipStream_t st)
 size_t colsum_scratch_floats(int rows, int C, int seg);
 int colsum(const float* a, const float* b, int rows, int C, int seg, float* out, int accumulate, float* scratch,
            hipStream_t st);
+int bcast_cols(const float* src, int n, float* dst, int ldd, int doff, int rows, int seg, hipStream_t st);
+size_t segsum_cols_scratch_floats(int rows, int n, int seg);
+int segsum_cols(const float* a, int lda, int soff, int n, int rows, int seg, float* out, int accumulate,
+                float* scratch, hipStream_t st);
 int sum_all(const float* a, const float* b, size_t n, float* out, float* scratch, hipStream_t st);
 
 int dropout(const float* a, size_t n, float p, unsigned seed, float* out, hipStream_t st);

@@ -11,6 +11,8 @@
 //               the gradient sum is deterministic)
 //   ew          elementwise with broadcasting (add / mul / masks / biases / activations and their gradients)
 //   colsum      segmented column sums (bias / gamma / beta / time-bias / SnakeBeta parameter gradients)
+//   bcast_cols / segsum_cols   a per-utterance vector repeated over the frames into a column slice, and its
+//               adjoint (colsum read in place from a column slice): the speaker conditioning's concat
 //   groupnorm, layernorm  forward (saving mean / rstd) and backward
 //   softmax     row softmax with the reference's mask modes (decoder: masked keys := +3.4e38, model.py:697;
 //               encoder: masked scores := -1e4, model.py:353) and its backward
@@ -491,6 +493,27 @@ int copy_cols(const float* src, int lds, int soff, float* dst, int ldd, int doff
   return 0;
 }
 
+// dst[r][doff + j] = src[r / seg][j] for r < rows, j < n: one vector per utterance repeated over its seg rows into
+// a column slice (spks.unsqueeze(-1).repeat + cat, model.py:528, 977-979)
+__global__ void bcast_cols_kernel(const float* __restrict__ src, int n, float* __restrict__ dst, int ldd, int doff,
+                                  int rows, int seg) {
+  const size_t total = (size_t)rows * n;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / n;
+    const int j = (int)(i % n);
+    dst[r * ldd + doff + j] = src[(r / seg) * n + j];
+  }
+}
+
+int bcast_cols(const float* src, int n, float* dst, int ldd, int doff, int rows, int seg, hipStream_t st) {
+  MT_REQUIRE(src && dst && rows > 0 && n > 0 && doff >= 0 && doff + n <= ldd, "bcast_cols: args");
+  MT_REQUIRE(seg > 0 && rows % seg == 0, "bcast_cols: rows must be whole segments");
+  hipLaunchKernelGGL(bcast_cols_kernel, ew_grid((size_t)rows * n), dim3(256), 0, st, src, n, dst, ldd, doff, rows,
+                     seg);
+  MT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // sequence_mask (model.py:42-46): out[b][t] = t < lengths[b]
 __global__ void seq_mask_kernel(const long long* __restrict__ len, int B, int T, float* __restrict__ out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * T; i += gridDim.x * blockDim.x)
@@ -509,8 +532,10 @@ int seq_mask(const long long* lengths, int B, int T, float* out, hipStream_t st)
 // no atomics: partials over blocks of CS_ROWS rows (a 256-thread block = 64 columns x 4 row lanes, lanes combined
 // in lane order), then each segment's partials (4 threads per column over interleaved partials, combined in order).
 constexpr int CS_ROWS = 512;
+// a (and b) are read from the column slice [off, off + C) of rows lda floats apart (colsum: lda = C, off = 0)
 __global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                          int rows, int C, int seg, int nsub, float* __restrict__ part) {
+                                                          int lda, int off, int rows, int C, int seg, int nsub,
+                                                          float* __restrict__ part) {
   __shared__ float red[4][64];
   const int cl = threadIdx.x & 63, lr = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, sb = blockIdx.y;
   const int s = sb / nsub, k = sb % nsub;
@@ -518,7 +543,7 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const float* __restric
   float acc = 0.f;
   if (c < C)
     for (int r = r0 + lr; r < r1; r += 4) {
-      const size_t o = (size_t)r * C + c;
+      const size_t o = (size_t)r * lda + off + c;
       acc += b ? a[o] * b[o] : a[o];
     }
   red[lr][cl] = acc;
@@ -552,10 +577,28 @@ int colsum(const float* a, const float* b, int rows, int C, int seg, float* out,
   MT_REQUIRE(a && out && scratch && rows > 0 && C > 0 && seg > 0, "colsum: args");
   const int nseg = (rows + seg - 1) / seg, nsub = (seg + CS_ROWS - 1) / CS_ROWS;
   MT_REQUIRE((size_t)nseg * nsub <= 65535u * 64, "colsum: too many partial blocks");
-  hipLaunchKernelGGL(colsum_part_kernel, dim3((C + 63) / 64, nseg * nsub), dim3(256), 0, st, a, b, rows, C, seg,
-                     nsub, scratch);
+  hipLaunchKernelGGL(colsum_part_kernel, dim3((C + 63) / 64, nseg * nsub), dim3(256), 0, st, a, b, C, 0, rows, C,
+                     seg, nsub, scratch);
   hipLaunchKernelGGL(colsum_merge_kernel, dim3((C + 63) / 64, nseg), dim3(256), 0, st, (const float*)scratch, C,
                      nsub, out, accumulate);
+  MT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// out[s][j] (+)= sum over the rows of segment s of a[r * lda + soff + j], j < n: colsum read in place from a column
+// slice (the adjoint of bcast_cols; same two fixed-order levels, out and the partials n wide)
+size_t segsum_cols_scratch_floats(int rows, int n, int seg) { return colsum_scratch_floats(rows, n, seg); }
+
+int segsum_cols(const float* a, int lda, int soff, int n, int rows, int seg, float* out, int accumulate,
+                float* scratch, hipStream_t st) {
+  MT_REQUIRE(a && out && scratch && rows > 0 && n > 0 && soff >= 0 && soff + n <= lda, "segsum_cols: args");
+  MT_REQUIRE(seg > 0 && rows % seg == 0, "segsum_cols: rows must be whole segments");
+  const int nseg = rows / seg, nsub = (seg + CS_ROWS - 1) / CS_ROWS;
+  MT_REQUIRE((size_t)nseg * nsub <= 65535u, "segsum_cols: too many partial blocks");
+  hipLaunchKernelGGL(colsum_part_kernel, dim3((n + 63) / 64, nseg * nsub), dim3(256), 0, st, a, (const float*)nullptr,
+                     lda, soff, rows, n, seg, nsub, scratch);
+  hipLaunchKernelGGL(colsum_merge_kernel, dim3((n + 63) / 64, nseg), dim3(256), 0, st, (const float*)scratch, n, nsub,
+                     out, accumulate);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -118,6 +118,9 @@ SIGNATURES = {
     "mtt_seq_mask": (c_int, [P, c_int, c_int, P, P]),
     "mtt_colsum_scratch_floats": (c_size_t, [c_int, c_int, c_int]),
     "mtt_colsum": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, P]),
+    "mtt_bcast_cols": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P]),
+    "mtt_segsum_cols_scratch_floats": (c_size_t, [c_int, c_int, c_int]),
+    "mtt_segsum_cols": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P]),
     "mtt_sum": (c_int, [P, P, c_size_t, P, P, P]),
     "mtt_dropout": (c_int, [P, c_size_t, c_float, c_uint, P, P]),
     "mtt_groupnorm_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),

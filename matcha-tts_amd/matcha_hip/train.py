@@ -15,7 +15,10 @@ the backward has produced its last gradient, overlapping the collective with the
 Adam runs once over the flat parameter buffer.
 
 Arithmetic: fp32 (the reference trains under "16-mixed" autocast; this is the higher-precision parity
-mode). Multi-speaker conditioning (spk_emb) raises ``NotImplementedError``.
+mode), or 16-bit GEMM operands (``precision``). Multi-speaker models (n_spks > 1) look the batch's speaker ids
+up in ``spk_emb.weight`` and concatenate that vector over time onto the encoder's prenet output and onto the
+estimator's input (``mtt_bcast_cols``); the backward reduces those column slices back per utterance
+(``mtt_segsum_cols``) and writes the table gradient once, last.
 """
 from __future__ import annotations
 
@@ -188,6 +191,45 @@ def split_cols(d, Ca):
     check(lib().mtt_copy_cols(d.data_ptr(), C, 0, a.data_ptr(), Ca, 0, rows, Ca, 0, _s(d)), "split")
     check(lib().mtt_copy_cols(d.data_ptr(), C, Ca, b.data_ptr(), C - Ca, 0, rows, C - Ca, 0, _s(d)), "split")
     return a, b
+
+
+def take_cols(d, off, n):
+    """d[..][off : off + n] as a contiguous tensor"""
+    C = d.shape[-1]
+    out = empty(*d.shape[:-1], n, like=d)
+    check(lib().mtt_copy_cols(d.data_ptr(), C, off, out.data_ptr(), n, 0, d.numel() // C, n, 0, _s(d)), "take_cols")
+    return out
+
+
+def cat_spks(parts, spks, seg):
+    """[parts[0] | parts[1] | ... | spks[b]]: channel concat of [B][seg][Ci] activations with the speaker vector
+    [B][E] repeated over the seg frames"""
+    W = sum(p.shape[-1] for p in parts) + spks.shape[-1]
+    out, off = empty(*parts[0].shape[:-1], W, like=parts[0]), 0
+    for p in parts:
+        Ci = p.shape[-1]
+        check(lib().mtt_copy_cols(p.data_ptr(), Ci, 0, out.data_ptr(), W, off, p.numel() // Ci, Ci, 0, _s(p)), "cat")
+        off += Ci
+    return bcast_cols(spks, out, off, seg)
+
+
+def bcast_cols(src, dst, doff, seg):
+    """dst[..][doff : doff + n] = src [B][n] repeated over the seg rows of each utterance (the speaker vector's
+    unsqueeze + repeat + cat, model.py:528, 977-979); the rest of dst is left as it is"""
+    n, ldd = src.shape[-1], dst.shape[-1]
+    check(lib().mtt_bcast_cols(src.data_ptr(), n, dst.data_ptr(), ldd, doff, dst.numel() // ldd, seg, _s(dst)),
+          "bcast_cols")
+    return dst
+
+
+def segsum_cols(a, soff, n, seg, out, acc=False):
+    """out [B][n] (+)= the sum over each utterance's seg rows of a[..][soff : soff + n] (bcast_cols' adjoint)"""
+    lda = a.shape[-1]
+    rows = a.numel() // lda
+    scr = _Scratch.get(lib().mtt_segsum_cols_scratch_floats(rows, n, seg), a)
+    check(lib().mtt_segsum_cols(a.data_ptr(), lda, soff, n, rows, seg, out.data_ptr(), int(acc), scr.data_ptr(),
+                                _s(a)), "segsum_cols")
+    return out
 
 
 def colsum(a, C, out, b=None, seg=None, acc=False):
@@ -585,8 +627,9 @@ class EstimatorTrainer:
                p + ".attn1.to_k.weight", p + ".attn1.to_v.weight", p + ".norm1.weight", p + ".norm1.bias")
         return dx
 
-    def forward(self, x, mu, m0, t, seed):
-        """x (y_t), mu (mu_y) [B][T][80], m0 (y_mask) [B][T], t [B] -> pred [B][T][80] (masked), ctx"""
+    def forward(self, x, mu, m0, t, seed, spks=None):
+        """x (y_t), mu (mu_y) [B][T][80], m0 (y_mask) [B][T], t [B], spks [B][E] (multi-speaker: the input is
+        [y_t | mu_y | spks[b]], model.py:975-979) -> pred [B][T][80] (masked), ctx"""
         P = self.P
         B, T, F = x.shape
         half = self.c_cond // 2
@@ -601,7 +644,7 @@ class EstimatorTrainer:
         m1 = empty(B, T // 2, like=x)  # masks[-1][:, :, ::2]
         ew(AXPBY, m1, b=m0, beta=1.0, bc=(1, T // 2, 2, T // 2, B, T))
         c = {"emb": emb, "h1": h1, "s1": s1, "temb": temb, "mtemb": mtemb, "m0": m0, "m1": m1}
-        h = cat_cols(x, mu)
+        h = cat_cols(x, mu) if spks is None else cat_spks((x, mu), spks, T)
         h, c["d0r"] = self.resnet_fwd("down_blocks.0.0", h, m0, mtemb)
         h, c["d0t"] = self.tblock_fwd("down_blocks.0.1.0", h, m0, seed + 1)
         h0 = h
@@ -627,7 +670,8 @@ class EstimatorTrainer:
         return linear_fwd(c["fp_in"], P["final_proj.weight"], P["final_proj.bias"], rmask=m0).view(B, T, F), c
 
     def backward(self, dpred, c, G):
-        """dpred [B][T][80] -> d mu [B][T][80]; parameter gradients into G (estimator-relative names)."""
+        """dpred [B][T][80] -> d mu [B][T][80], d spks [B][E] (None without a speaker vector); parameter gradients
+        into G (estimator-relative names)."""
         P = self.P
         B, T, F = dpred.shape
         m0, m1, mtemb = c["m0"], c["m1"], c["mtemb"]
@@ -670,7 +714,8 @@ class EstimatorTrainer:
                    G.view["time_mlp.linear_1.weight"], G.view["time_mlp.linear_1.bias"], need_dx=False)
         G.done("time_mlp.linear_2.weight", "time_mlp.linear_2.bias", "time_mlp.linear_1.weight",
                "time_mlp.linear_1.bias")
-        return split_cols(dxin, F)[1]
+        E = dxin.shape[-1] - 2 * F  # dxin: [d y_t | d mu_y | d spks repeated over the frames]
+        return take_cols(dxin, F, F), (segsum_cols(dxin, 2 * F, E, T, empty(B, E, like=dxin)) if E else None)
 
 
 # -------------------------------------------------------------------------------------------- the encoder
@@ -684,8 +729,9 @@ class EncoderTrainer:
                  p_dp=0.1):
         self.P, self.L, self.H = P, n_layers, heads
         self.p, self.p_pre, self.p_dp = p_drop, p_prenet, p_dp
-        self.C = P["emb.weight"].shape[1]
-        self.dh = self.C // heads
+        self.C = P["emb.weight"].shape[1]  # the embedding and the prenet
+        self.W = P["proj_m.weight"].shape[1]  # the layers after the speaker concat: C + spk_emb_dim (model.py:484-497)
+        self.dh = self.W // heads
         self.d_rope = int(self.dh * 0.5)
         self.theta = rt.rope_theta(self.dh).to(P["emb.weight"].device)
         self.prenet = "prenet.proj.weight" in P
@@ -698,8 +744,12 @@ class EncoderTrainer:
     def cln_bwd(self, dy, ctx, p, G):
         return ln_bwd(dy, ctx, self.P[p + ".gamma"], G.view[p + ".gamma"], G.view[p + ".beta"])
 
-    def forward(self, x_ids, x_lengths, seed):
-        P, C = self.P, self.C
+    def forward(self, x_ids, x_lengths, seed, spks=None):
+        """spks [B][W - C]: the looked-up speaker vectors, concatenated over the text after the prenet
+        (model.py:526-529)"""
+        P, C, D = self.P, self.C, self.W
+        if (spks.shape[-1] if spks is not None else 0) != D - C:
+            raise ValueError(f"encoder layers are {D} wide over {C} channels: a speaker vector of {D - C} is needed")
         B, Tx = x_ids.shape
         dev = P["emb.weight"]
         xm = seq_mask(x_lengths, Tx, dev)
@@ -717,17 +767,19 @@ class EncoderTrainer:
                 pre.append((cc, lc, n))
             c["pre"], c["pre_last"] = pre, h
             h = mul_rows(add(org, linear_fwd(h, P["prenet.proj.weight"], P["prenet.proj.bias"]).view(B, Tx, C)), xm)
+        if spks is not None:
+            h = cat_spks((h,), spks, Tx)
         layers = []
         for i in range(self.L):
             a, s = f"encoder.attn_layers.{i}", seed + 10 + 4 * i
             hm = mul_rows(h, xm)
-            q = linear_fwd(hm, P[a + ".conv_q.weight"], P[a + ".conv_q.bias"]).view(B, Tx, C)
-            k = linear_fwd(hm, P[a + ".conv_k.weight"], P[a + ".conv_k.bias"]).view(B, Tx, C)
-            v = linear_fwd(hm, P[a + ".conv_v.weight"], P[a + ".conv_v.bias"]).view(B, Tx, C)
+            q = linear_fwd(hm, P[a + ".conv_q.weight"], P[a + ".conv_q.bias"]).view(B, Tx, D)
+            k = linear_fwd(hm, P[a + ".conv_k.weight"], P[a + ".conv_k.bias"]).view(B, Tx, D)
+            v = linear_fwd(hm, P[a + ".conv_v.weight"], P[a + ".conv_v.bias"]).view(B, Tx, D)
             rope_(q, self.H, self.dh, self.d_rope, self.theta)
             rope_(k, self.H, self.dh, self.d_rope, self.theta)
             o, ac = attention_fwd(q, k, v, xm, xm, self.H, self.dh, 1.0 / math.sqrt(self.dh), 1, self.p, s)
-            y = linear_fwd(o, P[a + ".conv_o.weight"], P[a + ".conv_o.bias"]).view(B, Tx, C)
+            y = linear_fwd(o, P[a + ".conv_o.weight"], P[a + ".conv_o.bias"]).view(B, Tx, D)
             h1, l1 = self.cln(add(hm, dropout(y, self.p, s + 1)), f"encoder.norm_layers_1.{i}")
             f = f"encoder.ffn_layers.{i}"
             f1, c1 = conv_fwd(h1, P[f + ".conv_1.weight"], P[f + ".conv_1.bias"], pad=self.k // 2, mask=xm)
@@ -750,9 +802,10 @@ class EncoderTrainer:
         c["dp"] = (d1, dc1, dl1, d2, dc2, dl2, n2m)
         return mu, logw, xm, c
 
-    def backward(self, dmu, dlogw, c, G):
-        """dmu [B][Tx][80], dlogw [B][Tx] -> parameter gradients into G (TextEncoder-relative names)."""
-        P, C = self.P, self.C
+    def backward(self, dmu, dlogw, c, G, dspks=None):
+        """dmu [B][Tx][80], dlogw [B][Tx] -> parameter gradients into G (TextEncoder-relative names); multi-speaker:
+        the speaker vector's gradient is ADDED to dspks [B][W - C]."""
+        P, C, D = self.P, self.C, self.W
         xm, seed = c["xm"], c["seed"]
         B, Tx, _ = dmu.shape
         # duration predictor: its input is detached, nothing flows back into the encoder
@@ -768,7 +821,7 @@ class EncoderTrainer:
                  need_dx=False)
         G.done_prefix("proj_w.")
         dh = linear_bwd(mul_rows(dmu, xm), c["hm"], P["proj_m.weight"], G.view["proj_m.weight"],
-                        G.view["proj_m.bias"]).view(B, Tx, C)
+                        G.view["proj_m.bias"]).view(B, Tx, D)
         dh = mul_rows(dh, xm)
         G.done("proj_m.weight", "proj_m.bias")
         for i in reversed(range(self.L)):
@@ -782,16 +835,19 @@ class EncoderTrainer:
                                    G.view[f + ".conv_1.bias"]))
             ds1 = self.cln_bwd(dh1, l1, f"encoder.norm_layers_1.{i}", G)  # d(hm + drop(attn))
             do = linear_bwd(dropout(ds1, self.p, s + 1), o, P[a + ".conv_o.weight"], G.view[a + ".conv_o.weight"],
-                            G.view[a + ".conv_o.bias"]).view(B, Tx, C)
+                            G.view[a + ".conv_o.bias"]).view(B, Tx, D)
             dq, dk, dv = attention_bwd(do, ac)
             rope_(dq, self.H, self.dh, self.d_rope, self.theta, inverse=True)
             rope_(dk, self.H, self.dh, self.d_rope, self.theta, inverse=True)
             dhm = ds1
             for nm, dd in (("conv_q", dq), ("conv_k", dk), ("conv_v", dv)):
                 dhm = add(dhm, linear_bwd(dd, hm, P[f"{a}.{nm}.weight"], G.view[f"{a}.{nm}.weight"],
-                                          G.view[f"{a}.{nm}.bias"]).view(B, Tx, C))
+                                          G.view[f"{a}.{nm}.bias"]).view(B, Tx, D))
             dh = mul_rows(dhm, xm)
             G.done_prefix(a + ".", f + ".", f"encoder.norm_layers_1.{i}.", f"encoder.norm_layers_2.{i}.")
+        if D > C:  # [d prenet output | d spks repeated over the text]
+            segsum_cols(dh, C, D - C, Tx, dspks, acc=True)
+            dh = take_cols(dh, 0, C)
         if self.prenet:
             dorg = dh  # h = (org + proj(r)) * m, dh already masked
             drd = linear_bwd(dh, c["pre_last"], P["prenet.proj.weight"], G.view["prenet.proj.weight"],
@@ -826,11 +882,12 @@ def log_prior(mu_x, y_btc):
 
 
 class MatchaTrainer:
-    """Training step of the Matcha-TTS acoustic model (single speaker) on the GPU.
+    """Training step of the Matcha-TTS acoustic model (single- or multi-speaker) on the GPU.
 
-    state: the MatchaTTS state dict ("encoder.*", "decoder.estimator.*" reference names); hp: encoder
-    hyper-parameters (n_layers, n_heads). Parameters, gradients and Adam moments live in flat fp32 buffers
-    on ``device``; ``parameters()`` / ``gradients()`` return reference-named views."""
+    state: the MatchaTTS state dict ("encoder.*", "decoder.estimator.*" reference names, and "spk_emb.weight"
+    when hp["n_spks"] > 1); hp: encoder hyper-parameters (n_layers, n_heads, n_spks). Parameters, gradients and
+    Adam moments live in flat fp32 buffers on ``device``; ``parameters()`` / ``gradients()`` return reference-named
+    views."""
 
     def __init__(self, state: Dict[str, torch.Tensor], hp: dict, device, lr: float = 1e-4, sigma_min: float = 1e-4,
                  prior_loss: bool = True, dropout: bool = True, grad_clip: float = 5.0, heads: int = 2,
@@ -847,10 +904,14 @@ class MatchaTrainer:
         and the step skipped on an inf / NaN gradient, x2 after 2000 finite steps); "bf16-mixed": bf16 operands, no
         scaler. Activations, norms, softmax, losses and the Adam state stay fp32 in every mode; the log-prior / MAS
         products and the alignment GEMMs (0/1 attn) stay exact fp32."""
-        if int(hp.get("n_spks", 1)) > 1:
-            raise NotImplementedError("multi-speaker training (spk_emb conditioning) is not built")
-        names = [k for k, v in state.items() if k.startswith(("encoder.", "decoder.estimator."))
-                 and torch.is_floating_point(v)]
+        self.n_spks = int(hp.get("n_spks", 1))
+        if self.n_spks > 1 and "spk_emb.weight" not in state:
+            raise KeyError("n_spks > 1: the state needs the speaker table 'spk_emb.weight'")
+        # the speaker table is registered first (model.py MatchaTTS), so in the reverse-order flat buffer it lies
+        # last: that is where the backward finishes
+        names = (["spk_emb.weight"] if self.n_spks > 1 else []) + [
+            k for k, v in state.items() if k.startswith(("encoder.", "decoder.estimator."))
+            and torch.is_floating_point(v)]
         self.names = names
         shapes = [(k, tuple(state[k].shape)) for k in reversed(names)]  # the backward fills the buffer in order
         dev = torch.device(device)
@@ -925,17 +986,30 @@ class MatchaTrainer:
         return dict(self.grads.view)
 
     def forward_backward(self, x, x_lengths, y, y_lengths, t: Optional[torch.Tensor] = None,
-                         z: Optional[torch.Tensor] = None, backward: bool = True):
+                         z: Optional[torch.Tensor] = None, backward: bool = True,
+                         spks: Optional[torch.Tensor] = None):
         """train_standalone.py:623-667 + the backward of dur + prior + cfm. x int64 [B][Tx], y [B][80][Ty]
         (Ty % 4 == 0, the collate's fix_len_compatibility), lengths int64 [B]; t [B] / z [B][80][Ty] default to
         the reference's draws (torch.rand, torch.randn_like). Leaves the all-reduced (summed over ranks)
         gradients in the flat buffer; returns the losses as device scalars. backward=False: losses only
-        (validation_step)."""
+        (validation_step). spks: int64 speaker ids [B], looked up in spk_emb.weight (:625-628); ignored by a
+        single-speaker model, required when n_spks > 1."""
         rt.require_gpu(x, y, what="MatchaTrainer")
         lo, hi = (int(v) for v in torch.aminmax(x))  # nn.Embedding raises on an out-of-vocabulary id
         n_vocab = self.params.view["encoder.emb.weight"].shape[0]
         if lo < 0 or hi >= n_vocab:
             raise IndexError(f"token id out of range [0, {n_vocab}): min {lo}, max {hi}")
+        if self.n_spks > 1:
+            if spks is None:
+                raise ValueError(f"n_spks = {self.n_spks}: the step needs the batch's speaker ids (spks is None)")
+            spks = spks.to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+            if spks.numel() != x.shape[0]:
+                raise ValueError(f"spks: one id per utterance, got {spks.numel()} for a batch of {x.shape[0]}")
+            lo, hi = (int(v) for v in torch.aminmax(spks))
+            if lo < 0 or hi >= self.n_spks:
+                raise IndexError(f"speaker id out of range [0, {self.n_spks}): min {lo}, max {hi}")
+        else:
+            spks = None
         B, Tx = x.shape
         F, Ty = y.shape[1], y.shape[2]
         if Ty % 4:
@@ -953,14 +1027,20 @@ class MatchaTrainer:
         self.calls += 1
         self.buckets.reset()
         with operand_format(self.opfmt):
-            return self._forward_backward(x, xl, y, yl, t, z, seed, backward)
+            return self._forward_backward(x, xl, y, yl, t, z, seed, backward, spks)
 
-    def _forward_backward(self, x, xl, y, yl, t, z, seed, backward):
+    def _forward_backward(self, x, xl, y, yl, t, z, seed, backward, spk_ids=None):
         B, Tx = x.shape
         F, Ty = y.shape[1], y.shape[2]
         S = self.scaler["scale"] if self.scaler else 1.0  # the loss scale seeds the backward
         # ---- forward
-        mu_x, logw, xm, ectx = self.enc.forward(x, xl, seed)
+        spks = None
+        if spk_ids is not None:  # self.spk_emb(spks), train_standalone.py:626: fp32 in every precision mode
+            table = self.params.view["spk_emb.weight"]
+            spks = empty(B, table.shape[1], like=y)
+            check(lib().mtt_embed_fwd(spk_ids.data_ptr(), B, table.data_ptr(), table.shape[1], 1.0, spks.data_ptr(),
+                                      _s(y)), "spk_emb")
+        mu_x, logw, xm, ectx = self.enc.forward(x, xl, seed, spks)
         ym = seq_mask(yl, Ty, y)
         y_btc, z_btc = transpose(y, B, F, Ty), transpose(z, B, F, Ty)
         lp = log_prior(mu_x, y_btc)
@@ -976,7 +1056,7 @@ class MatchaTrainer:
         bcb = (Ty * F, B, 1, 1, 1, 0)
         y_t = add(ew(MUL, like_(z_btc), z_btc, coef, bc=bcb), ew(MUL, like_(y_btc), y_btc, t, bc=bcb))
         u_t = add(y_btc, z_btc, beta=-(1.0 - self.sigma_min))
-        pred, dctx = self.est.forward(y_t, mu_y, ym, t, seed + 128)
+        pred, dctx = self.est.forward(y_t, mu_y, ym, t, seed + 128, spks)
         n80 = mul_scalar(total(ym), ones(1, y), alpha=float(F))
         inv_n80 = ew(RECIP, empty(1, like=y), n80, alpha=1.0)
         diff = add(pred, u_t, beta=-1.0)
@@ -1002,12 +1082,17 @@ class MatchaTrainer:
                          "log_prior": lp}
             return self.last
         # ---- backward
-        dmu_y = self.est.backward(dpred, dctx, Grads(self.grads, "decoder.estimator.", self.buckets))
+        dmu_y, dspks = self.est.backward(dpred, dctx, Grads(self.grads, "decoder.estimator.", self.buckets))
         if self.prior:
             add(dmu_y, mul_scalar(mul_rows(ymu, ym, alpha=-S), inv_n80), out=dmu_y)
         dmu_x = empty(B, Tx, F, like=y)
         gemm(attn, dmu_y, Tx, F, Ty, dmu_x, batch=B, sA=Tx * Ty, sB=Ty * F, sC=Tx * F)
-        self.enc.backward(dmu_x, dlogw, ectx, Grads(self.grads, "encoder.", self.buckets))
+        self.enc.backward(dmu_x, dlogw, ectx, Grads(self.grads, "encoder.", self.buckets), dspks)
+        if spk_ids is not None:  # the estimator's d spks, held, plus the encoder's -> one table gradient, last
+            g = self.grads.view["spk_emb.weight"]
+            check(lib().mtt_embed_bwd(spk_ids.data_ptr(), B, dspks.data_ptr(), g.shape[0], g.shape[1], 1.0,
+                                      g.data_ptr(), _s(y)), "spk_emb_bwd")
+            self.buckets.mark("spk_emb.weight")
         self.buckets.finish()
         loss = add(add(dur, prior), cfm)
         self.last = {"loss": loss, "dur_loss": dur, "prior_loss": prior, "cfm_loss": cfm, "attn": attn,
@@ -1053,8 +1138,6 @@ class MatchaTrainer:
         return self.last
 
     def training_step(self, batch: dict):
-        """train_standalone.py:669-685: batch with x, x_lengths, y, y_lengths -> losses (device scalars)."""
-        if batch.get("spks") is not None:
-            raise NotImplementedError("multi-speaker training (spk_emb conditioning) is not built")
-        self.forward_backward(batch["x"], batch["x_lengths"], batch["y"], batch["y_lengths"])
+        """train_standalone.py:669-685: batch with x, x_lengths, y, y_lengths (and spks) -> losses (device scalars)."""
+        self.forward_backward(batch["x"], batch["x_lengths"], batch["y"], batch["y_lengths"], spks=batch.get("spks"))
         return self.optimizer_step()

@@ -14,7 +14,10 @@ the reference's methods and the semantics Lightning adds around them made explic
     opt.step(); opt.zero_grad()
 
 ``module.model`` is the drop-in ``model.MatchaTTS``; after ``opt.step()`` its parameters hold the trained
-weights, so ``module.model.synthesize(...)`` (and ``state_dict()``) see the update. The data module, the
+weights, so ``module.model.synthesize(...)`` (and ``state_dict()``) see the update. With ``n_spks > 1`` the
+module owns the speaker table the step trains (``module.spk_emb``, as in the reference, :604-605, :626);
+``module.model.spk_emb`` is a second, untrained table, so a caller passes ``module.spk_emb(ids)`` to
+``module.model.synthesize(spks=...)``. The data module, the
 CLI and the Lightning Trainer loop (:714-900) are out of scope.
 """
 from __future__ import annotations
@@ -87,9 +90,10 @@ class _FusedAdam:
         pass  # every backward overwrites the whole flat gradient buffer
 
     def _index(self):
-        """module.parameters() order -> trainer parameter name (the reference's Adam state is keyed by it)"""
-        names = [n for n, _ in self.module.named_parameters()]
-        return [n[len("model."):] if n.startswith("model.") else n for n in names]
+        """module.parameters() order -> trainer parameter name (the reference's Adam state is keyed by it), None
+        for a parameter the step does not train: the module-level speaker table is the engine's "spk_emb.weight";
+        the model's own table gets no gradient, so, as in torch's Adam, no state"""
+        return [self.module._engine_name(n) for n, _ in self.module.named_parameters()]
 
     def state_dict(self):
         tr = self.module.trainer()
@@ -138,15 +142,13 @@ class _FusedAdam:
 
 
 class MatchaLightningModule(torch.nn.Module):
-    """train_standalone.py:580-707 (single speaker). ``forward`` returns (dur_loss, prior_loss, cfm_loss, attn) like
-    the reference; in training mode it also runs the backward, leaving the gradients for ``optimizer.step()``."""
+    """train_standalone.py:580-707 (single- and multi-speaker). ``forward`` returns (dur_loss, prior_loss, cfm_loss,
+    attn) like the reference; in training mode it also runs the backward, leaving the gradients for ``optimizer.step()``."""
 
     def __init__(self, n_vocab, n_spks, spk_emb_dim, encoder_params, decoder_params, cfm_params,
                  duration_predictor_params, data_statistics, learning_rate=1e-4, prior_loss=True,
                  process_group=None, precision="32"):
         super().__init__()
-        if n_spks > 1:
-            raise NotImplementedError("multi-speaker training (spk_emb conditioning) is not built")
         self.learning_rate, self.n_vocab, self.n_spks = learning_rate, n_vocab, n_spks
         self.n_feats = _get(encoder_params, "n_feats")
         self.prior_loss = prior_loss
@@ -158,6 +160,8 @@ class MatchaLightningModule(torch.nn.Module):
                    "n_spks": n_spks}
         self.heads = _get(decoder_params, "num_heads", 2)
         self.sigma_min = _get(cfm_params, "sigma_min", 1e-4)
+        if n_spks > 1:  # train_standalone.py:604-605: the table the step trains, registered before the model
+            self.spk_emb = torch.nn.Embedding(n_spks, spk_emb_dim)
         self.model = _model.MatchaTTS(n_vocab, n_spks, spk_emb_dim, encoder_params, decoder_params, cfm_params,
                                       duration_predictor_params)
         self.register_buffer("mel_mean", torch.tensor(data_statistics["mel_mean"]))
@@ -176,11 +180,25 @@ class MatchaLightningModule(torch.nn.Module):
     def _world(self) -> int:
         return dist.get_world_size(self.process_group) if dist.is_available() and dist.is_initialized() else 1
 
+    @staticmethod
+    def _engine_name(n: str) -> Optional[str]:
+        """module parameter name -> the engine's name for it: the model's encoder / estimator tensors without the
+        "model." prefix and the module-level speaker table as "spk_emb.weight"; None for model.spk_emb.weight"""
+        if n == "spk_emb.weight":
+            return n
+        if n.startswith(("model.encoder.", "model.decoder.estimator.")):
+            return n[len("model."):]
+        return None
+
+    def _engine_state(self, keep_vars=False):
+        """the tensors the engine holds, under its names"""
+        sd = self.state_dict(keep_vars=keep_vars)
+        return {self._engine_name(k): v for k, v in sd.items() if self._engine_name(k) is not None}
+
     def _model_fp(self):
         """(address, version) of the tensors the engine holds (the buffers mel_mean / mel_std are not among them:
         _broadcast_buffers rewrites those every DDP step and must not trigger a parameter reload)"""
-        return [(t.data_ptr(), t._version) for k, t in self.model.state_dict(keep_vars=True).items()
-                if k.startswith(("encoder.", "decoder.estimator."))]
+        return [(t.data_ptr(), t._version) for t in self._engine_state(keep_vars=True).values()]
 
     def trainer(self) -> MatchaTrainer:
         """the GPU training engine, built from the model's current weights on first use; a later change of the
@@ -189,7 +207,7 @@ class MatchaLightningModule(torch.nn.Module):
         dev = self.mel_mean.device
         if self._tr is None or self._tr.params.flat.device != dev:
             rt.require_gpu(self.mel_mean, what="MatchaLightningModule")
-            self._tr = MatchaTrainer(self.model.state_dict(), self.hp, dev, lr=self.learning_rate,
+            self._tr = MatchaTrainer(self._engine_state(), self.hp, dev, lr=self.learning_rate,
                                      sigma_min=self.sigma_min, prior_loss=self.prior_loss, heads=self.heads,
                                      process_group=self.process_group, p_dropout=self.p_dropout,
                                      precision=self.precision)
@@ -197,7 +215,7 @@ class MatchaLightningModule(torch.nn.Module):
                 self._sync_model()  # the ranks' modules hold rank 0's weights, as under DDP
             self._fp = self._model_fp()
         elif self._model_fp() != self._fp:
-            self._tr.load_parameters(self.model.state_dict())
+            self._tr.load_parameters(self._engine_state())
             self._fp = self._model_fp()
         if self._pending_opt is not None:
             opt, self._pending_opt = self._pending_opt, None
@@ -206,7 +224,7 @@ class MatchaLightningModule(torch.nn.Module):
 
     @torch.no_grad()
     def _sync_model(self):
-        sd = self.model.state_dict(keep_vars=True)
+        sd = self._engine_state(keep_vars=True)
         for k, v in self._tr.parameters().items():
             sd[k].data.copy_(v)
         self._fp = self._model_fp()
@@ -235,11 +253,10 @@ class MatchaLightningModule(torch.nn.Module):
                             f"{prefix}/prior_loss": vals[2], f"{prefix}/cfm_loss": vals[3]})
 
     def forward(self, x, x_lengths, y, y_lengths, spks=None):
-        if spks is not None and self.n_spks > 1:
-            raise NotImplementedError("multi-speaker training (spk_emb conditioning) is not built")
+        """spks: int64 speaker ids [B] (the collate's batch["spks"]), looked up in self.spk_emb when n_spks > 1"""
         self._broadcast_buffers()
         tr = self.trainer().set_dropout(self.training)
-        out = tr.forward_backward(x, x_lengths, y, y_lengths, backward=self.training)
+        out = tr.forward_backward(x, x_lengths, y, y_lengths, backward=self.training, spks=spks)
         # attn: maximum_path's [B, T_x, T_y] as the reference returns it (train_standalone.py:646, 667)
         return out["dur_loss"][0], out["prior_loss"][0], out["cfm_loss"][0], out["attn"]
 

@@ -4,6 +4,10 @@ weights and data. Prints one JSON line: ms/step, mel frames/s, peak memory, and 
 its GEMMs / convs / attention against the precision's MFMA peak).
 
     python tools/train_bench.py [--batch 64] [--steps 5] [--warmup 2] [--no-dropout] [--precision 32|16-mixed|bf16-mixed]
+                                [--n-spks 109]
+
+--n-spks N > 1: the multi-speaker model (spk_emb_dim 64) with uniform random speaker ids in the batch; the line
+then carries "n_spks". The default 1 leaves the line as it is.
 """
 import argparse
 import json
@@ -18,18 +22,22 @@ sys.path.insert(0, os.path.join(ROOT, "matcha-tts_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def step_flops(B, Tx, Ty):
+def step_flops(B, Tx, Ty, spk=0):
     """GEMM / conv / attention FLOPs of one training step (forward x 3: forward, data and weight gradients) on the
     padded shapes the step computes: the text encoder + duration predictor on B x Tx tokens (prenet 3 x k = 5 convs +
     1x1, 6 RoPE layers: QKV, attention 2 x 2 x Tx x 192 per token, out-projection, FFN k = 3 192 <-> 768; proj_m;
     duration predictor k = 3 192 -> 256 -> 256 -> 1), and one estimator evaluation on B x Ty frames (bench.py's
-    per-frame decoder count)."""
+    per-frame decoder count). spk: the speaker vector's width (multi-speaker): everything after the
+    prenet is w = 192 + spk wide, and the estimator's first ResnetBlock (k = 3 conv + 1x1 res_conv into 256) reads spk
+    more input channels."""
     import bench
     c, f, dp = 192, 768, 256
+    w = c + spk
     enc = (3 * 2 * c * c * 5 + 2 * c * c
-           + 6 * (3 * 2 * c * c + 2 * c * c + 2 * 2 * Tx * c + 2 * (2 * c * f * 3))
-           + 2 * c * 80 + 2 * c * dp * 3 + 2 * dp * dp * 3 + 2 * dp)
-    return 3 * (B * Tx * enc + B * Ty * bench.dec_flops_per_frame_step(Ty))
+           + 6 * (3 * 2 * w * w + 2 * w * w + 2 * 2 * Tx * w + 2 * (2 * w * f * 3))
+           + 2 * w * 80 + 2 * w * dp * 3 + 2 * dp * dp * 3 + 2 * dp)
+    dec = bench.dec_flops_per_frame_step(Ty) + 2 * spk * 256 * 3 + 2 * spk * 256
+    return 3 * (B * Tx * enc + B * Ty * dec)
 
 
 def main():
@@ -39,12 +47,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--precision", default="32")
+    ap.add_argument("--n-spks", type=int, default=1)
     a = ap.parse_args()
     from conftest import HP, make_matcha
     from matcha_hip import synthetic
     from matcha_hip.train import MatchaTrainer
     dev = torch.device("cuda")
-    m = make_matcha(1, "fp32")
+    m = make_matcha(a.n_spks, "fp32")
     sd = {k: torch.from_numpy(v) for k, v in synthetic.make_state_dict(
         [(k, tuple(v.shape)) for k, v in m.state_dict().items()], 1234).items()}
     B = a.batch
@@ -55,24 +64,25 @@ def main():
     x = torch.randint(1, 178, (B, Tx), generator=g) * (torch.arange(Tx)[None] < xl[:, None])
     y = torch.randn(B, 80, Ty, generator=g) * (torch.arange(Ty)[None, None] < yl[:, None, None])
     args = [t.to(dev) for t in (x, xl, y, yl)]
-    tr = MatchaTrainer(sd, HP, dev, dropout=not a.no_dropout, precision=a.precision)
+    kw = {"spks": torch.randint(0, a.n_spks, (B,), generator=g).to(dev)} if a.n_spks > 1 else {}
+    tr = MatchaTrainer(sd, dict(HP, n_spks=a.n_spks), dev, dropout=not a.no_dropout, precision=a.precision)
     for _ in range(a.warmup):
-        tr.forward_backward(*args)
+        tr.forward_backward(*args, **kw)
         tr.optimizer_step()
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        tr.forward_backward(*args)
+        tr.forward_backward(*args, **kw)
         tr.optimizer_step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / a.steps
     frames = int(yl.sum())
     sys.path.insert(0, ROOT)
-    flops = step_flops(B, Tx, Ty)
+    flops = step_flops(B, Tx, Ty, spk=64 if a.n_spks > 1 else 0)
     # the GEMM operands' arithmetic: exact fp32 MFMA (157.3 TF) in "32", fp16 / bf16 MFMA (2.5 PF dense) when mixed
     peak = 157.3e12 if a.precision == "32" else 2.5e15
-    print(json.dumps({"what": "cfm_training_step", "batch": B, "Tx": Tx, "Ty": Ty, "mel_frames": frames,
+    print(json.dumps({"what": "cfm_training_step", **({"n_spks": a.n_spks} if a.n_spks > 1 else {}), "batch": B, "Tx": Tx, "Ty": Ty, "mel_frames": frames,
                       "ms_per_step": round(ms, 2), "mel_frames_per_s": round(frames / ms * 1e3, 1),
                       "params": int(tr.params.flat.numel()), "peak_gb": round(torch.cuda.max_memory_allocated() / 1e9, 2),
                       "loss": round(float(tr.last["loss"]), 4), "dropout": not a.no_dropout,
