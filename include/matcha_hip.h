@@ -405,7 +405,12 @@ int mt_ffn_set(int enable);
 int mt_ffn_set_min_frames(int frames);
 /* Decoder kernel variants (mask; each bit-identical to the launches it replaces): bit 0 the final projection + ODE
  * update (final_proj of mish(GroupNorm) * mask, z += dt * v) on a dedicated kernel instead of the generic conv
- * kernel. Default 1 (MT_DECK=<mask> in the environment); process-wide; returns the previous mask. */
+ * kernel; bit 1 the query-independent attention's per-utterance output vector o_b (bf16 decoder, utterances with
+ * padding) computed in the first estimator evaluation of a mt_cfm_solve only and kept per transformer block for the
+ * later ones: it depends on the weights and on the number of masked frames, not on the ODE state, the time, mu or the
+ * speaker, so recomputing it (two launches per block and evaluation) gives the same bits. Never kept across solves or
+ * graph replays; single evaluations (mt_decoder_step) always compute it. Default 3 (MT_DECK=<mask> in the
+ * environment); process-wide; returns the previous mask. */
 int mt_decoder_set_kernels(int mask);
 /* qkv [B][T][3*heads*64], mask [B][T] -> out [B][T][heads*64], reference mask semantics */
 int mt_op_attention(int dtype, const void* qkv, const float* mask, void* out, int B, int T, int heads,
@@ -440,10 +445,17 @@ int mt_probe_stop(int* launches, double* total_ms, double* flops, double* bytes,
 /* Launch log of the persistent LDS-DMA conv (test coverage only; no reference counterpart). While
  * armed, every mt_vconv launch appends 11 int32: epilogue flags, rows per tile (BM), frames per tile
  * (BN), 1x1 pipeline flag, output tiles, grid size (tiles > grid: workgroups walk several tiles), taps,
- * output channels, input channels, utterances, frames per utterance. stop returns the record count. */
+ * output channels, input channels, utterances, frames per utterance. stop returns the record count.
+ * Launches of other kernels carry a tag in the first field instead of epilogue flags: 0x20000 the decoder's final
+ * projection + ODE update kernel; and, only after mt_vconv_log_select(3), 0x40000 / 0x80000 / 0xC0000 the
+ * query-independent attention's masked-sum pass, its per-utterance vector (o_b) and its x += o_b pass (grid size in
+ * fields 5-6, utterances and frames per utterance in the last two) and 0x400000 the fused decoder FeedForward (field 4:
+ * 1 when it adds o_b itself). mt_vconv_log_select: bit 0 the conv launches (always on), bit 1 those other decoder
+ * launches (off by default: readers of the conv log expect conv variants); process-wide; returns the previous mask. */
 #define MT_VCONV_LOG_FIELDS 11
 int mt_vconv_log_start(int capacity);
 int mt_vconv_log_stop(int32_t* records, int capacity);
+int mt_vconv_log_select(int families);
 
 #ifdef __cplusplus
 }

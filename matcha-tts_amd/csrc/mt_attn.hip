@@ -18,6 +18,7 @@
 // and for an utterance without padding the ordinary softmax over all keys applies.
 #include "mt_common.h"
 #include "mt_misc.h"
+#include "mt_probe.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -513,23 +514,37 @@ __global__ __launch_bounds__(256) void attn_uni_apply_kernel(bf16* __restrict__ 
 int uniform_part_slices(int T) { return std::max(1, std::min(UNI_PSMAX, T / 24)); }
 size_t uniform_attention_floats(int B) { return (size_t)B * (UNI_PSMAX * UNI_PART + UNI_C); }
 
-const float* uniform_attention_ovec(const float* part, int B) { return part + (size_t)B * UNI_PSMAX * UNI_PART; }
+// [B][256] after the slice sums (uniform_attention_floats): the o_b of a caller that keeps none of its own
+float* uniform_attention_ovec(float* part, int B) { return part + (size_t)B * UNI_PSMAX * UNI_PART; }
 
-int launch_uniform_attention(void* x, const float* mask, int B, int T, const void* wqkv, int mq, const float* bqkv,
-                             const void* wout, const float* bout, float* part, float* row_out, hipStream_t st,
-                             bool apply) {
-  MT_REQUIRE(x && mask && wqkv && bqkv && wout && bout && part && (row_out || !apply) && B > 0 && T > 0 && mq == 384,
+// launch-log record of one uniform-attention launch (tags UNI_LOG_*, mt_misc.h)
+static void uniform_log(int tag, int grid, int B, int T) {
+  const int rec[VCLOG_FIELDS] = {tag, UNI_C, 0, 0, grid, grid, 0, UNI_C, UNI_C, B, T};
+  vclog_record(rec, VCLOG_AUX);
+}
+
+int launch_uniform_ovec(const void* x, const float* mask, int B, int T, const void* wqkv, int mq, const float* bqkv,
+                        const void* wout, const float* bout, float* part, float* ovec, hipStream_t st) {
+  MT_REQUIRE(x && mask && wqkv && bqkv && wout && bout && part && ovec && B > 0 && T > 0 && mq == 384,
              "uniform attention: arguments (C = 256, 2 heads x 64)");
   const int SP = uniform_part_slices(T);
-  float* ovec = part + (size_t)B * UNI_PSMAX * UNI_PART;  // [B][256] after the slice sums (uniform_attention_floats)
   const int xr = xcd_remap_for((size_t)B * T * UNI_C * sizeof(bf16));
   hipLaunchKernelGGL(attn_uni_part_kernel, dim3(SP, B), dim3(256), 0, st, (const bf16*)x, mask, T, part, xr);
   hipLaunchKernelGGL(attn_uni_vec_kernel, dim3(B), dim3(256), 0, st, SP, (const float*)part, (const bf16*)wqkv, mq,
                      bqkv, (const bf16*)wout, bout, ovec);
-  if (apply)
-    hipLaunchKernelGGL(attn_uni_apply_kernel, dim3(SP, B), dim3(256), 0, st, (bf16*)x, T, (const float*)ovec, row_out,
-                     xr);
   MT_CHECK_HIP(hipGetLastError());
+  uniform_log(UNI_LOG_PART, SP * B, B, T);
+  uniform_log(UNI_LOG_VEC, B, B, T);
+  return 0;
+}
+
+int launch_uniform_apply(void* x, int B, int T, const float* ovec, float* row_out, hipStream_t st) {
+  MT_REQUIRE(x && ovec && row_out && B > 0 && T > 0, "uniform attention apply: arguments");
+  const int SP = uniform_part_slices(T);
+  const int xr = xcd_remap_for((size_t)B * T * UNI_C * sizeof(bf16));
+  hipLaunchKernelGGL(attn_uni_apply_kernel, dim3(SP, B), dim3(256), 0, st, (bf16*)x, T, ovec, row_out, xr);
+  MT_CHECK_HIP(hipGetLastError());
+  uniform_log(UNI_LOG_APPLY, SP * B, B, T);
   return 0;
 }
 

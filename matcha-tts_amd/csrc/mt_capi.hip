@@ -558,5 +558,6 @@ int mtt_unscale(float* g, size_t n, float inv_scale, float* found, float* scratc
 
 int mt_vconv_log_start(int capacity) { return mt::vclog_start(capacity); }
 int mt_vconv_log_stop(int32_t* records, int capacity) { return mt::vclog_stop(records, capacity); }
+int mt_vconv_log_select(int families) { return mt::vclog_select(families); }
 
 }  // extern "C"

@@ -421,6 +421,7 @@ size_t Decoder::workspace_bytes(int B, int T, int S) const {
   n += align256(BT * (C / 64) * 2 * 4);               // lnp
   n += align256(uniform_attention_floats(B) * 4);     // upart
   n += align256(BT * 4);                              // mst
+  n += align256((size_t)n_tblocks() * B * C * 4);     // uvec
   return n;
 }
 
@@ -462,6 +463,7 @@ Decoder::Work Decoder::carve(void* ws, int B, int T, int S) const {
   w.lnp = (float*)take(BT * (C / 64) * 2 * 4);
   w.upart = (float*)take(uniform_attention_floats(B) * 4);
   w.mst = (float*)take(BT * 4);
+  w.uvec = (float*)take((size_t)n_tblocks() * B * C * 4);
   w.m0 = nullptr;
   return w;
 }
@@ -616,7 +618,7 @@ int Decoder::resnet(const char* P, const Work& w, const Res& R, const void* x0, 
 
 template <class E>
 int Decoder::tblock(const char* P, const Work& w, const TB& t, void* x, const float* mask, bool mask_out,
-                    bool row_stats, bool uni, int B, int Tl, hipStream_t st) const {
+                    bool row_stats, bool uni, float* uslot, bool ucached, int B, int Tl, hipStream_t st) const {
   int rc;
   if constexpr (std::is_same<E, bf16>::value) {
     if (t.qkv.vc && t.out.vc && t.ff1.vc && t.ff2.vc) {
@@ -662,12 +664,17 @@ int Decoder::tblock(const char* P, const Work& w, const TB& t, void* x, const fl
       };
       if (uni && heads == 2 && t.qkv.cout == 384 && t.qkv.cin == C && t.out.cout == C && t.out.cin == 128) {
         // every utterance is padded at this level: attention is query-independent (model.py:697) -> x += o_b
-        // with o_b from a masked mean and two GEMVs; no QKV GEMM, no attention, no per-frame out-projection
-        if ((rc = launch_uniform_attention(x, mask, B, Tl, P + t.qkv.v_off, t.qkv.cout, (const float*)(P + t.qkv.b_off),
-                                           P + t.out.v_off, (const float*)(P + t.out.b_off), w.upart, w.lnp, st,
-                                           !fused_ff)))
+        // with o_b from a masked mean and two GEMVs; no QKV GEMM, no attention, no per-frame out-projection.
+        // o_b is the same in every evaluation of a solve (the masked frames' rows never change): with
+        // DECK_OVEC the first evaluation leaves it in the block's slot and the later ones (ucached) only add it
+        float* ovec = uslot ? uslot : uniform_attention_ovec(w.upart, B);
+        if (!ucached && (rc = launch_uniform_ovec(x, mask, B, Tl, P + t.qkv.v_off, t.qkv.cout,
+                                                  (const float*)(P + t.qkv.b_off), P + t.out.v_off,
+                                                  (const float*)(P + t.out.b_off), w.upart, ovec, st)))
           return rc;
-        return feedforward(fused_ff ? uniform_attention_ovec(w.upart, B) : nullptr);
+        if (fused_ff) return feedforward(ovec);
+        if ((rc = launch_uniform_apply(x, B, Tl, ovec, w.lnp, st))) return rc;
+        return feedforward(nullptr);
       }
       // LayerNorm statistics: per-slab partials from the producing conv's epilogue (VE_ROWSTATS) when it
       // wrote them, else a row-statistics pass
@@ -735,11 +742,17 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
   // transformer block of a chain, the down/up convs), so mt_vconv needs no input prologue
   const bool mio = vconv && std::is_same<E, bf16>::value;
   bool rs = false;  // the last resnet's output conv wrote the LayerNorm partials of its output
+  // DECK_OVEC: transformer block j of resnet r keeps its o_b in slot (blocks before resnet r) + j of w.uvec;
+  // evaluation 0 of the chain (and a single evaluation: step, step_times) computes it, the later ones read it
+  const bool ovk = std::is_same<E, bf16>::value && (dec_kernels() & DECK_OVEC);
   auto tblocks = [&](int r, void* x, const float* m, int Tl) -> int {
     const int nb = (int)tbs[r].size();
     const bool uni = uniform_attn && (Tl == T ? w.uni0 : w.uni1);
+    size_t slot = 0;
+    for (int i = 0; i < r; ++i) slot += tbs[i].size();
     for (int j = 0; j < nb; ++j) {
-      int e = tblock<E>(P, w, tbs[r][j], x, m, mio && j == nb - 1, rs && j == 0, uni, B, Tl, st);
+      float* us = ovk ? w.uvec + (slot + j) * (size_t)B * C : nullptr;
+      int e = tblock<E>(P, w, tbs[r][j], x, m, mio && j == nb - 1, rs && j == 0, uni, us, ovk && ev > 0, B, Tl, st);
       if (e) return e;
     }
     return 0;

@@ -18,7 +18,7 @@ struct FfnArgs {
   const bf16* w2;         // mt_vconv 1x1 image of ff.net.2: [16][256][64]
   const float* b2;        // [256]
   const float* emask;     // [frames] or null: y *= mask (the chain's last block hands out a masked copy)
-  // the query-independent attention's output (mt_attn.hip, launch_uniform_attention with apply = false): when set,
+  // the query-independent attention's output (mt_attn.hip, launch_uniform_ovec without launch_uniform_apply): when set,
   // the tile's rows are first updated x = bf16(x + ovec[utterance]) in LDS and the LayerNorm partials computed there
   // (attn_uni_apply_kernel's arithmetic; ln_stats unused)
   const float* ovec;      // [B][256] or null
@@ -30,6 +30,9 @@ struct FfnArgs {
 // the fused kernel for the bf16 decoder's shape (C = 256, inner 1024); MT_FFN=0 in the environment or
 // mt_ffn_set(0): the two mt_vconv launches instead (same bits)
 int launch_ffn(const FfnArgs& a, hipStream_t st);
+// launch-log tag (the record's ef field; mt_probe.h vclog_record, family VCLOG_AUX) of a launch_ffn; its k1 field: 1
+// with ovec set
+constexpr int FFN_LOG = 0x400000;
 int ffn_set(int enable);  // -> the previous setting
 int ffn_on();
 // the fused kernel runs on levels of at least this many frames (B * T; default 16384 = 128 128-frame tiles,

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "mt_ffn.h"
+#include "mt_probe.h"
 #include "mt_vconv.h"
 
 #ifndef FFN_NVE
@@ -664,6 +665,9 @@ int launch_ffn(const FfnArgs& a, hipStream_t st) {
                   : (a.emask ? ffn_kernel<true, false, false> : ffn_kernel<false, false, false>);
   hipLaunchKernelGGL(kern, dim3(G), dim3(FNT), 0, st, a);
   MT_CHECK_HIP(hipGetLastError());
+  const int rec[VCLOG_FIELDS] = {FFN_LOG, FC, FBN, a.ovec ? 1 : 0, ntiles, G, 1, FC, FC, a.T > 0 ? a.frames / a.T : 0,
+                                 a.T > 0 ? a.T : a.frames};
+  vclog_record(rec, VCLOG_AUX);
   return 0;
 }
 

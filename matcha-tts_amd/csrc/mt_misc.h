@@ -74,13 +74,18 @@ size_t attention_part_bytes(int B, int T, int heads);
 // utterance the merge and the two GEMVs (o_b); x += o_b with the row statistics over the same slices.
 constexpr int UNI_PSMAX = 32;  // most masked-sum slices per utterance (the workspace holds B x 32 x 260 floats)
 int uniform_part_slices(int T);
-size_t uniform_attention_floats(int B);  // workspace of launch_uniform_attention's `part`: slice sums + o_b
-// apply = false: the first two launches only; o_b ([B][256] floats) is left at uniform_attention_ovec(part, B) for a
-// consumer that adds it itself (mt_ffn)
-int launch_uniform_attention(void* x, const float* mask, int B, int T, const void* wqkv, int mq, const float* bqkv,
-                             const void* wout, const float* bout, float* part, float* row_out, hipStream_t st,
-                             bool apply = true);
-const float* uniform_attention_ovec(const float* part, int B);
+size_t uniform_attention_floats(int B);  // workspace `part`: slice sums + one o_b ([B][256] floats)
+float* uniform_attention_ovec(float* part, int B);  // the o_b inside `part`
+// The caller chooses the steps. launch_uniform_ovec: the first two launches, o_b -> ovec ([B][256] floats; x is only
+// read). o_b depends on the rows of x at the masked frames only, so a caller that knows them unchanged (the ODE
+// solve's later evaluations) keeps ovec and skips this step. launch_uniform_apply: the third launch from a
+// given ovec; a consumer that adds o_b itself (mt_ffn, FfnArgs::ovec) replaces it.
+int launch_uniform_ovec(const void* x, const float* mask, int B, int T, const void* wqkv, int mq, const float* bqkv,
+                        const void* wout, const float* bout, float* part, float* ovec, hipStream_t st);
+int launch_uniform_apply(void* x, int B, int T, const float* ovec, float* row_out, hipStream_t st);
+// launch-log tags (the record's ef field; mt_probe.h vclog_record, family VCLOG_AUX) of the three launches: part, vec,
+// apply
+enum : int { UNI_LOG_PART = 0x40000, UNI_LOG_VEC = 0x80000, UNI_LOG_APPLY = 0xC0000 };
 
 // the XCD-aligned block order of the decoder's streaming kernels (mt_common.h xcd_chunk; MT_XCD_TILES=0 turns it
 // and mt_vconv's XCD-major tile walk off)

@@ -59,9 +59,11 @@ ConvArgs gemm_args(const GemmW& g, const char* P, int B, int Tin);
 size_t align256(size_t x);
 
 // Decoder kernel variants, each bit-identical to the launches it replaces (mt_decoder_set_kernels): DECK_PROJ the
-// final projection + ODE update on proj_euler_kernel (mt_conv.hip) instead of the generic conv kernel. On by
+// final projection + ODE update on proj_euler_kernel (mt_conv.hip) instead of the generic conv kernel; DECK_OVEC the
+// query-independent attention's o_b computed in the first evaluation of a solve only and kept per transformer block
+// for the later ones (it does not depend on the ODE state), instead of two launches per block and evaluation. On by
 // default; MT_DECK=<mask> in the environment (read once) or dec_set_kernels() to change.
-enum : int { DECK_PROJ = 1, DECK_ALL = 1 };
+enum : int { DECK_PROJ = 1, DECK_OVEC = 2, DECK_ALL = 3 };
 int dec_kernels();
 int dec_set_kernels(int mask);  // -> the previous mask
 
@@ -111,6 +113,8 @@ struct Decoder {
     float* apart;  // attention key-split slots
     float* lnp;    // per frame, per 64-channel slab (sum, sum of squares): LayerNorm partials (vconv VE_ROWSTATS)
     float* upart;  // query-independent attention: per (utterance, slice) masked sums of the normalised rows
+    float* uvec;   // ... its o_b per transformer block, [n_tblocks()][B][256] (DECK_OVEC): written by the first
+                   // evaluation of a solve_chain, read by the later ones
     float* mst;    // the solve's staged copy of the caller's mask (graph replays read only the workspace)
     int tb_ld;     // 0: one time bias per evaluation; n_res * C: one per utterance (step_times)
     const float* m0;
@@ -137,9 +141,15 @@ struct Decoder {
              hipStream_t st) const;
   // row_stats: w.lnp already holds the LayerNorm partials of x (written by the producing conv)
   template <class E>
-  // uni: the query-independent attention path (every utterance padded at this level)
+  // uni: the query-independent attention path (every utterance padded at this level); uslot: this block's o_b slot
+  // in w.uvec, or null for the shared one; ucached: the slot holds this solve's o_b, compute nothing
   int tblock(const char* P, const Work& w, const TB& t, void* x, const float* mask, bool mask_out, bool row_stats,
-             bool uni, int B, int Tl, hipStream_t st) const;
+             bool uni, float* uslot, bool ucached, int B, int Tl, hipStream_t st) const;
+  int n_tblocks() const {
+    size_t n = 0;
+    for (const auto& v : tbs) n += v.size();
+    return (int)n;
+  }
   bool vc(const GemmW& g) const { return vconv && g.vc; }
   // decoder input row stride: zero-padded to a multiple of 64 channels (and stored masked) on the vconv path
   int xld() const { return (vconv && dtype == BF16) ? (c_cond + 63) / 64 * 64 : c_cond; }

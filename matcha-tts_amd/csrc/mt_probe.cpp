@@ -152,8 +152,16 @@ int sched_get(int i, int* rec, int* wait, int* wait_first, int cap) {
   return t[i].waits(wait, wait_first, cap);
 }
 
-void vclog_record(const int (&rec)[VCLOG_FIELDS]) {
-  if (!g_log_on) return;
+static int g_log_sel = VCLOG_CONV;
+int vclog_select(int families) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int prev = g_log_sel;
+  g_log_sel = (families & (VCLOG_CONV | VCLOG_AUX)) | VCLOG_CONV;
+  return prev;
+}
+
+void vclog_record(const int (&rec)[VCLOG_FIELDS], int family) {
+  if (!g_log_on || !(g_log_sel & family)) return;
   std::lock_guard<std::mutex> lk(g_mu);
   if ((int)g_log.size() >= g_log_cap * VCLOG_FIELDS) return;
   g_log.insert(g_log.end(), rec, rec + VCLOG_FIELDS);

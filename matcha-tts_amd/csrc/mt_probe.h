@@ -33,7 +33,12 @@ int probe_stop(int* launches, double* total_ms, double* flops, double* bytes, do
 // the grid it used, so parity tests can show which instantiations ran and whether workgroups walked
 // more than one tile. Host-only state, off unless vclog_start() armed it.
 constexpr int VCLOG_FIELDS = 11;  // ef, BM, BN, K1, ntiles, grid, taps, M, cin, B, L
-void vclog_record(const int (&rec)[VCLOG_FIELDS]);
+// record families: VCLOG_CONV the conv launches (mt_vconv, the pair kernels, proj_euler_kernel), always taken;
+// VCLOG_AUX the decoder's other launches (the query-independent attention's three kernels, the fused FeedForward),
+// taken only after vclog_select(VCLOG_CONV | VCLOG_AUX): the conv log's readers expect conv variants only
+enum : int { VCLOG_CONV = 1, VCLOG_AUX = 2 };
+void vclog_record(const int (&rec)[VCLOG_FIELDS], int family = VCLOG_CONV);
+int vclog_select(int families);  // -> the previous selection (VCLOG_CONV is always on)
 int vclog_start(int cap);
 int vclog_stop(int* out, int cap);  // -> records written (cap records of VCLOG_FIELDS ints)
 bool vclog_armed();

@@ -139,6 +139,7 @@ SIGNATURES = {
     "mtt_unscale": (c_int, [P, c_size_t, c_float, P, P, P]),
     "mt_vconv_log_start": (c_int, [c_int]),
     "mt_vconv_log_stop": (c_int, [P, c_int]),
+    "mt_vconv_log_select": (c_int, [c_int]),
 }
 
 _lib = None

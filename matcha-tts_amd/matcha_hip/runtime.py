@@ -650,7 +650,8 @@ def set_ffn_min_frames(frames: int) -> int:
 
 
 def set_decoder_kernels(mask: int) -> int:
-    """the decoder kernel variants (bit 0: the dedicated final projection + ODE update kernel; default 1), each
+    """the decoder kernel variants (bit 0: the dedicated final projection + ODE update kernel; bit 1: the
+    query-independent attention's o_b computed once per solve instead of once per evaluation; default 3), each
     bit-identical to what it replaces; returns the previous mask (process-wide)"""
     return int(lib().mt_decoder_set_kernels(int(mask)))
 
@@ -719,6 +720,20 @@ def probe_stop(peak_flops: float = 2.5e15, peak_bw: float = 8.0e12) -> Dict[str,
 
 
 VCONV_LOG_FIELDS = ("ef", "bm", "bn", "k1", "ntiles", "grid", "taps", "M", "cin", "B", "L")
+# "ef" of the launches that are not mt_vconv's: a tag instead of epilogue flags. PROJ_LOG proj_euler_kernel. Only
+# after vconv_log_select(LOG_CONV | LOG_AUX): the query-independent attention's three launches (attn_uni_part_kernel,
+# attn_uni_vec_kernel, attn_uni_apply_kernel; grid in "grid", utterances in "B", frames per utterance in "L") and
+# FFN_LOG the fused FeedForward (k1 = 1: it adds o_b itself)
+PROJ_LOG = 0x20000
+UNI_LOG_PART, UNI_LOG_VEC, UNI_LOG_APPLY = 0x40000, 0x80000, 0xC0000
+FFN_LOG = 0x400000
+LOG_CONV, LOG_AUX = 1, 2
+
+
+def vconv_log_select(families: int) -> int:
+    """which launches the log records: LOG_CONV the conv launches (always), LOG_AUX also the decoder's uniform-attention
+    and fused-FeedForward launches (off by default); returns the previous selection (process-wide)"""
+    return int(lib().mt_vconv_log_select(int(families)))
 
 
 def vconv_log_start(capacity: int = 65536) -> None:

@@ -2,7 +2,8 @@
 """In-process A/B of the decoder kernel variants (mt_decoder_set_kernels masks, bit-identical): the bf16 CFM solve
 (10-step Euler, graph path) at B x T, ragged like the bench (the longest utterance T - 4 frames, so the
 query-independent attention runs at both levels), interleaved rounds, median and min per mask; checks the outputs
-are equal. Usage: python tools/deck_ab.py [B] [T] [rounds] [masks, e.g. 0,1]"""
+are equal. Default: mask 1 (o_b recomputed in every evaluation) against mask 3 (o_b once per solve).
+Usage: python tools/deck_ab.py [B] [T] [rounds] [masks, e.g. 0,1]"""
 import os
 import sys
 import time
@@ -19,7 +20,7 @@ from matcha_hip import synthetic  # noqa: E402
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 728
 R = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-MASKS = [int(c) for c in sys.argv[4].split(",")] if len(sys.argv) > 4 else [0, 1]
+MASKS = [int(c) for c in sys.argv[4].split(",")] if len(sys.argv) > 4 else [1, 3]
 dec = make_decoder(160, "bf16")
 sd = synthetic.make_state_dict([(k, tuple(v.shape)) for k, v in dec.state_dict().items()], 7)
 dec.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
