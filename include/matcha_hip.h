@@ -139,6 +139,23 @@ int mt_cfm_solve(const mt_decoder* d, const void* packed, const float* z_noise, 
 int mt_cfm_solve_bounded(const mt_decoder* d, const void* packed, const float* z_noise, float temperature,
                          const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
                          int n_timesteps, int solver, float* z_out, void* ws, size_t ws_bytes, void* stream);
+/* mt_cfm_solve_bounded with the noise drawn by the library instead of read from z_noise: utterance b gets the seeded
+ * stream of seeds[b] (int64 [B], device; see mt_noise_fill) times temperature[b] (fp32 [B], device; NULL = 1), at
+ * every frame of [0, T), padded ones included. One kernel writes the solver's fp32 state and the estimator's input
+ * slot directly, so no [B,80,T] noise tensor exists; it runs before the captured graph, which is the same graph
+ * mt_cfm_solve_bounded replays. Bit-identical to mt_cfm_solve_bounded on z_noise = mt_noise_fill(seeds, temperature)
+ * with temperature 1, and on z_noise = mt_noise_fill(seeds, NULL) with one shared temperature. Workspace:
+ * mt_cfm_workspace_bytes. */
+int mt_cfm_solve_seeded(const mt_decoder* d, const void* packed, const int64_t* seeds, const float* temperature,
+                        const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
+                        int n_timesteps, int solver, float* z_out, void* ws, size_t ws_bytes, void* stream);
+/* Seeded Gaussian noise, z [B,C,T] fp32 (C % 4 == 0): z[b,c,t] depends on (seeds[b], c, t) only, not on B, T or the
+ * row's position. Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) of the int64 seed's two's-complement uint64
+ * on the counter (t, c / 4, 0, 0); each output word x gives u(x) = (2 (x >> 9) + 1) 2^-24; channels 4q, 4q + 1 are
+ * r(u(x0)) cos(2 pi u(x1)) and r(u(x0)) sin(2 pi u(x1)), channels 4q + 2, 4q + 3 the same from x2, x3, with
+ * r(u) = sqrt(-2 ln u); the value is then multiplied by temperature[b] (fp32 [B], device; NULL = 1) in fp32.
+ * matcha_hip/noise.py is the same stream on the CPU. */
+int mt_noise_fill(const int64_t* seeds, const float* temperature, int B, int C, int T, float* z, void* stream);
 /* 1 (default): mt_cfm_solve_bounded takes the query-independent attention path where max_valid allows it;
  * 0: always the general Q.K^T path (A/B, tests) */
 int mt_decoder_set_uniform_attention(mt_decoder* d, int enable);
@@ -215,6 +232,10 @@ int mt_vocoder_ragged_supported(const mt_vocoder* v);
  * y_lengths = max(sum(w_ceil), 1) int64 [B]. */
 int mt_durations(const float* logw, const float* x_mask, float length_scale, int B, int Tx,
                  float* w_ceil, float* cum, int64_t* y_lengths, void* stream);
+/* the same with one length scale per utterance, length_scale fp32 [B] in device memory: row b has the bits of
+ * mt_durations on that row with length_scale[b] */
+int mt_durations_scaled(const float* logw, const float* x_mask, const float* length_scale, int B, int Tx,
+                        float* w_ceil, float* cum, int64_t* y_lengths, void* stream);
 /* attn [B,1,Tx,T] one-hot path (may be NULL); mu_y[b,c,j] = mu[b,c,token(j)] [B,C,T] (may be NULL);
  * y_mask [B,1,T] = (j < y_lengths[b]) (may be NULL) */
 int mt_alignment(const float* cum, const int64_t* y_lengths, int B, int Tx, int T, const float* mu, int C,

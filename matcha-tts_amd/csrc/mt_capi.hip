@@ -178,6 +178,21 @@ int mt_cfm_solve_bounded(const mt_decoder* d, const void* packed, const float* z
   return d->d.solve(packed, z_noise, temperature, mu_y, mask, spks, B, T, n_timesteps, solver, z_out, ws,
                     ws_bytes, (hipStream_t)stream, max_valid);
 }
+int mt_cfm_solve_seeded(const mt_decoder* d, const void* packed, const int64_t* seeds, const float* temperature,
+                        const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
+                        int n_timesteps, int solver, float* z_out, void* ws, size_t ws_bytes, void* stream) {
+  MT_REQUIRE(seeds, "cfm_solve_seeded: seeds is NULL");
+  MT_REQUIRE(d && packed && mu_y && mask && z_out && ws, "cfm_solve_seeded: null argument");
+  return d->d.solve(packed, nullptr, 1.f, mu_y, mask, spks, B, T, n_timesteps, solver, z_out, ws, ws_bytes,
+                    (hipStream_t)stream, max_valid, (const long long*)seeds, temperature);
+}
+int mt_noise_fill(const int64_t* seeds, const float* temperature, int B, int C, int T, float* z, void* stream) {
+  MT_REQUIRE(seeds, "noise_fill: seeds is NULL");
+  MT_REQUIRE(z, "noise_fill: z is NULL");
+  MT_REQUIRE(C > 0 && C % 4 == 0, "noise_fill: C %d must be a positive multiple of 4", C);
+  MT_REQUIRE(B > 0 && T > 0, "noise_fill: B %d and T %d must be positive", B, T);
+  return mt::noise_fill((const long long*)seeds, temperature, B, C, T, z, (hipStream_t)stream);
+}
 int mt_decoder_set_uniform_attention(mt_decoder* d, int enable) {
   MT_REQUIRE(d, "null decoder");
   d->d.uniform_attn = enable ? 1 : 0;
@@ -288,6 +303,13 @@ int mt_durations(const float* logw, const float* x_mask, float length_scale, int
   MT_REQUIRE(logw && x_mask && w_ceil && cum && y_lengths, "durations: null argument");
   return mt::durations(logw, x_mask, length_scale, B, Tx, w_ceil, cum, (long long*)y_lengths,
                        (hipStream_t)stream);
+}
+int mt_durations_scaled(const float* logw, const float* x_mask, const float* length_scale, int B, int Tx,
+                        float* w_ceil, float* cum, int64_t* y_lengths, void* stream) {
+  MT_REQUIRE(length_scale, "durations_scaled: length_scale is NULL");
+  MT_REQUIRE(logw && x_mask && w_ceil && cum && y_lengths, "durations_scaled: null argument");
+  return mt::durations(logw, x_mask, 1.f, B, Tx, w_ceil, cum, (long long*)y_lengths, (hipStream_t)stream,
+                       length_scale);
 }
 int mt_alignment(const float* cum, const int64_t* y_lengths, int B, int Tx, int T, const float* mu, int C,
                  float* attn, float* mu_y, float* y_mask, void* stream) {

@@ -876,12 +876,18 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
 }
 
 int Decoder::init_inputs(const Work& w, const float* z, float temperature, const float* mu_y,
-                         const float* spks, int B, int T, hipStream_t st) const {
+                         const float* spks, int B, int T, hipStream_t st, const long long* seeds,
+                         const float* temp_dev) const {
   int rc;
   const int ld = xld();
   if (ld != c_cond) MT_CHECK_HIP(hipMemsetAsync(w.xin, 0, (size_t)B * T * ld * esize, st));  // zero pad channels
-  if ((rc = bct_to_btc(F32, z, B, NF, T, temperature, w.zm, NF, 0, st))) return rc;
-  if ((rc = bct_to_btc(dtype, z, B, NF, T, temperature, w.xin, ld, 0, st))) return rc;
+  if (seeds) {
+    // the fp32 master and the z slot of xin straight from the generator: no [B,80,T] noise tensor to transpose
+    if ((rc = noise_fill_decoder(dtype, seeds, temp_dev, B, T, w.zm, w.xin, ld, st))) return rc;
+  } else {
+    if ((rc = bct_to_btc(F32, z, B, NF, T, temperature, w.zm, NF, 0, st))) return rc;
+    if ((rc = bct_to_btc(dtype, z, B, NF, T, temperature, w.xin, ld, 0, st))) return rc;
+  }
   if ((rc = bct_to_btc(dtype, mu_y, B, NF, T, 1.f, w.xin, ld, NF, st))) return rc;
   if (c_cond > 2 * NF) {
     MT_REQUIRE(spks != nullptr, "decoder: c_cond %d needs speaker embeddings", c_cond);
@@ -967,7 +973,8 @@ int Decoder::chain_graph(const char* P, const Work& w, const TimeSched& ts, int 
 
 int Decoder::solve(const void* packed, const float* z_noise, float temperature, const float* mu_y,
                    const float* mask, const float* spks, int B, int T, int n_steps, int solver, float* z_out,
-                   void* ws, size_t ws_bytes, hipStream_t st, int max_valid) const {
+                   void* ws, size_t ws_bytes, hipStream_t st, int max_valid, const long long* seeds,
+                   const float* temp_dev) const {
   int rc;
   if ((rc = check_geom(B, T))) return rc;
   MT_REQUIRE(n_steps >= 1, "cfm: n_timesteps must be >= 1");
@@ -999,14 +1006,14 @@ int Decoder::solve(const void* packed, const float* z_noise, float temperature, 
   // eager only while the decoder's own launches are probed or logged: an armed vocoder probe (bench.py's last timed
   // step) must not take the solve off its graph
   if (!(graphs && !probe_armed(PROBE_VCONV_DEC) && !vclog_armed())) {
-    if ((rc = init_inputs(w, z_noise, temperature, mu_y, spks, B, T, st))) return rc;
+    if ((rc = init_inputs(w, z_noise, temperature, mu_y, spks, B, T, st, seeds, temp_dev))) return rc;
     if ((rc = solve_chain(P, w, ts, S, B, T, n_steps, solver, st))) return rc;
     return btc_to_bct(F32, w.zm, NF, 0, B, NF, T, z_out, st);
   }
   // graph path: the chain reads only the packed weights and the workspace (inputs and mask staged into it)
   MT_CHECK_HIP(hipMemcpyAsync(w.mst, mask, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
   w.m0 = w.mst;
-  if ((rc = init_inputs(w, z_noise, temperature, mu_y, spks, B, T, st))) return rc;
+  if ((rc = init_inputs(w, z_noise, temperature, mu_y, spks, B, T, st, seeds, temp_dev))) return rc;
   hipGraphExec_t ex = nullptr;
   if ((rc = chain_graph(P, w, ts, S, B, T, n_steps, solver, ws, &ex))) return rc;
   MT_CHECK_HIP(hipGraphLaunch(ex, st));

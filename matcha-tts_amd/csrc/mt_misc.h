@@ -19,6 +19,13 @@ int bct_to_btc(int dtype, const float* src, int B, int C, int T, float scale, vo
                hipStream_t st);
 int btc_to_bct(int dtype, const void* src, int ld, int coff, int B, int C, int T, float* dst,
                hipStream_t st);
+// Seeded noise (mt_noise.hip): the value at (seeds[b], channel, frame) times temp[b] (temp NULL: 1), a pure function
+// of those. noise_fill: z [B][C][T] fp32, C % 4 == 0. noise_fill_decoder: the estimator's 80 channels into both
+// workspace layouts at once, zm [B][T][80] fp32 and columns 0 .. 79 of xin [B][T][ld] (element type by dtype, the
+// rounding of zm's value).
+int noise_fill(const long long* seeds, const float* temp, int B, int C, int T, float* z, hipStream_t st);
+int noise_fill_decoder(int dtype, const long long* seeds, const float* temp, int B, int T, float* zm, void* xin,
+                       int ld, hipStream_t st);
 int spk_fill(int dtype, const float* spks, int B, int C, int T, void* dst, int ld, int coff, hipStream_t st);
 int mask_half(const float* m0, int B, int T0, float* m1, hipStream_t st);
 // dst[r][0..C) = src[r][0..C) (row strides ld_src / ld_dst, element type by dtype)
@@ -49,8 +56,9 @@ struct RowdotSegs {
 int rowdot_segs(const float* x, int ldx, const RowdotSegs& sg, float* y, int ldy, int S, int O, int I, int pre,
                 int post, hipStream_t st);
 
+// ls_dev (optional): one length scale per utterance, [B] in device memory, read in place of ls
 int durations(const float* logw, const float* xmask, float ls, int B, int Tx, float* w_ceil, float* cum,
-              long long* ylen, hipStream_t st);
+              long long* ylen, hipStream_t st, const float* ls_dev = nullptr);
 int alignment(const float* cum, const long long* ylen, int B, int Tx, int T, const float* mu, int C, float* attn,
               float* mu_y, float* y_mask, hipStream_t st);
 int denorm_crop(const float* z, const float* mean, const float* stdv, int B, int C, int T, int Ty, float* mel,

@@ -400,8 +400,9 @@ int rowdot(const float* x, int ldx, const float* W, const float* bias, float* y,
 // an integer-valued fp32 (< 2^24), so sums and prefix sums are exact in any order.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict__ logw, const float* __restrict__ xmask,
-                                                        float ls, int Tx, float* __restrict__ w_ceil,
-                                                        float* __restrict__ cum, long long* __restrict__ ylen) {
+                                                        float ls0, const float* __restrict__ ls_dev, int Tx,
+                                                        float* __restrict__ w_ceil, float* __restrict__ cum,
+                                                        long long* __restrict__ ylen) {
   // chunks of 256 * DUR_PER tokens; in a chunk thread t owns the `per` consecutive tokens [t * per, (t + 1) * per):
   // ceil(exp(logw) * mask * ls), then an inclusive block scan of the per-thread sums (wave shuffles + one LDS pass)
   // on top of the previous chunks' total. Every value is an integer-valued fp32 below 2^24, so this order gives the
@@ -409,6 +410,7 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
   constexpr int DUR_PER = 32;
   __shared__ float wsum[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float ls = ls_dev ? ls_dev[b] : ls0;  // this utterance's length scale
   float base = 0.f;
   for (int c0 = 0; c0 < Tx; c0 += 256 * DUR_PER) {
     const int n = min(Tx - c0, 256 * DUR_PER);
@@ -451,9 +453,9 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
 }
 
 int durations(const float* logw, const float* xmask, float ls, int B, int Tx, float* w_ceil, float* cum,
-              long long* ylen, hipStream_t st) {
+              long long* ylen, hipStream_t st, const float* ls_dev) {
   MT_REQUIRE(B > 0 && Tx > 0, "durations: B %d, Tx %d", B, Tx);
-  hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, st, logw, xmask, ls, Tx, w_ceil, cum, ylen);
+  hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, st, logw, xmask, ls, ls_dev, Tx, w_ceil, cum, ylen);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -155,12 +155,16 @@ struct Decoder {
   int xld() const { return (vconv && dtype == BF16) ? (c_cond + 63) / 64 * 64 : c_cond; }
   VConvArgs vargs(const GemmW& g, const char* P, const Work& w, const void* x, int B, int Tl, void* y) const;
 
+  // seeds (optional, [B] in device memory): the noise is drawn here by noise_fill_decoder, scaled per utterance by
+  // temp_dev ([B] in device memory, or null for 1); z and temperature are then unused
   int init_inputs(const Work& w, const float* z, float temperature, const float* mu_y, const float* spks,
-                  int B, int T, hipStream_t st) const;
-  // max_valid: the most valid (mask = 1) frames of any utterance (0: unknown)
+                  int B, int T, hipStream_t st, const long long* seeds = nullptr,
+                  const float* temp_dev = nullptr) const;
+  // max_valid: the most valid (mask = 1) frames of any utterance (0: unknown); seeds / temp_dev: see init_inputs
   int solve(const void* packed, const float* z_noise, float temperature, const float* mu_y,
             const float* mask, const float* spks, int B, int T, int n_steps, int solver, float* z_out,
-            void* ws, size_t ws_bytes, hipStream_t st, int max_valid = 0) const;
+            void* ws, size_t ws_bytes, hipStream_t st, int max_valid = 0, const long long* seeds = nullptr,
+            const float* temp_dev = nullptr) const;
   // 1 (default): the query-independent attention path when the caller's max_valid allows it; 0: always the
   // general Q.K^T path (A/B, tests)
   int uniform_attn = 1;

@@ -51,6 +51,8 @@ SIGNATURES = {
     "mt_cfm_solve": (c_int, [P, P, P, c_float, P, P, P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     "mt_cfm_solve_bounded": (c_int, [P, P, P, c_float, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t,
                                      P]),
+    "mt_cfm_solve_seeded": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "mt_noise_fill": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "mt_decoder_set_uniform_attention": (c_int, [P, c_int]),
     "mt_decoder_set_graphs": (c_int, [P, c_int]),
     "mt_decoder_set_taps": (c_int, [P, P, c_int]),
@@ -73,6 +75,7 @@ SIGNATURES = {
     "mt_vocoder_forward_ragged": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "mt_vocoder_ragged_supported": (c_int, [P]),
     "mt_durations": (c_int, [P, P, c_float, c_int, c_int, P, P, P, P]),
+    "mt_durations_scaled": (c_int, [P, P, P, c_int, c_int, P, P, P, P]),
     "mt_alignment": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "mt_denorm_crop": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "mt_denoise_workspace_bytes": (c_size_t, [c_int, c_int]),

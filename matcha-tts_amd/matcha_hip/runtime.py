@@ -7,6 +7,7 @@ library only enqueues kernels on the current stream. All entry points require CU
 from __future__ import annotations
 
 import math
+import numbers
 import time
 from ctypes import byref, c_char_p, c_int, c_int64, c_void_p, create_string_buffer
 from typing import Dict, List, Optional, Tuple
@@ -294,16 +295,27 @@ class DecoderEngine:
         check(lib().mt_decoder_set_graphs(self.h, int(bool(enable))), "decoder_set_graphs")
 
     def solve(self, packed, z_noise, temperature, mu_y, mask, spks, n_timesteps, solver="euler",
-              out=None, max_valid: int = 0):
-        """max_valid: the most valid frames of any utterance (synthesize's y_max), 0 when unknown."""
+              out=None, max_valid: int = 0, seeds=None):
+        """max_valid: the most valid frames of any utterance (synthesize's y_max), 0 when unknown. seeds (int64 [B]
+        or B ints): utterance b starts from the seeded stream of seeds[b] (``seeded_noise``) drawn inside the solve,
+        z_noise is not read (pass None) and temperature is a number or one value per utterance."""
         B, C, T = mu_y.shape
         s = SOLVER_EULER if solver == "euler" else SOLVER_MIDPOINT if solver == "midpoint" else None
         if s is None:
             raise NotImplementedError(f"Solver {solver} not implemented")
+        if seeds is None and not is_scalar(temperature):
+            raise TypeError("solve: one temperature per utterance needs seeds (or scale z_noise per row and pass 1.0)")
         out = torch.empty_like(mu_y) if out is None else out
         L = lib()
         nbytes = L.mt_cfm_workspace_bytes(self.h, B, T, n_timesteps, s)
         ws = _Workspace.get(nbytes, mu_y.device)
+        if seeds is not None:
+            sd = seed_tensor(seeds, B, mu_y.device)
+            temp = per_row(temperature, B, mu_y.device, "temperature")
+            check(L.mt_cfm_solve_seeded(self.h, packed.data_ptr(), ptr(sd), ptr(temp), ptr(mu_y), ptr(mask),
+                                        ptr(spks), B, T, int(max_valid), int(n_timesteps), s, ptr(out),
+                                        ws.data_ptr(), ws.numel(), stream_handle(mu_y.device)), "cfm_solve_seeded")
+            return out
         check(L.mt_cfm_solve_bounded(self.h, packed.data_ptr(), ptr(z_noise), float(temperature), ptr(mu_y),
                                      ptr(mask), ptr(spks), B, T, int(max_valid), int(n_timesteps), s, ptr(out),
                                      ws.data_ptr(), ws.numel(), stream_handle(mu_y.device)), "cfm_solve")
@@ -471,14 +483,66 @@ def fetch_ints(t: torch.Tensor) -> List[int]:
     return buf.tolist()
 
 
-def durations(logw: torch.Tensor, x_mask: torch.Tensor, length_scale: float):
-    """model.py:1273-1275 -> (w_ceil [B,1,Tx], cum [B,Tx], y_lengths int64 [B])."""
+def is_scalar(v) -> bool:
+    """a Python / numpy number or a 0-d tensor: one value for the whole batch"""
+    return isinstance(v, numbers.Real) or (isinstance(v, torch.Tensor) and v.dim() == 0)
+
+
+def per_row(v, B: int, device, name: str) -> torch.Tensor:
+    """a number, or one value per utterance ([B] tensor or sequence) -> fp32 [B] on `device`"""
+    if is_scalar(v):
+        return torch.full((B,), float(v), dtype=torch.float32, device=device)
+    t = torch.as_tensor(v).detach().to(device=device, dtype=torch.float32).contiguous()
+    if t.shape != (B,):
+        raise ValueError(f"{name} {tuple(t.shape)}: expected a number or one value per utterance, ({B},)")
+    return t
+
+
+def seed_tensor(seeds, B: int, device) -> torch.Tensor:
+    """seeds: int64 [B] tensor or a sequence of B ints -> int64 [B] on `device`. A bare int is refused: it could
+    mean one stream shared by every utterance or a base seed to derive B streams from."""
+    if isinstance(seeds, numbers.Number) or (isinstance(seeds, torch.Tensor) and seeds.dim() == 0):
+        raise TypeError("seeds: one int64 seed per utterance ([B] tensor or sequence), not a bare int")
+    t = torch.as_tensor(seeds)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError(f"seeds: integer seeds expected, got {t.dtype}")
+    t = t.detach().to(device=device, dtype=torch.int64).contiguous()
+    if t.shape != (B,):
+        raise ValueError(f"seeds {tuple(t.shape)}: expected one seed per utterance, ({B},)")
+    return t
+
+
+def seeded_noise(seeds: torch.Tensor, T: int, temperature=None, C: int = 80) -> torch.Tensor:
+    """The seeded noise stream (matcha_hip/noise.py is its CPU specification) -> fp32 [B,C,T] on the seeds' device:
+    row b is a function of (seeds[b], channel, frame) only, times temperature (None: 1; a number or [B])."""
+    if not isinstance(seeds, torch.Tensor):
+        raise TypeError("seeded_noise: seeds is an int64 [B] tensor on the GPU (its device is the result's)")
+    require_gpu(seeds, what="seeded_noise")
+    if seeds.dim() != 1:
+        raise ValueError(f"seeds {tuple(seeds.shape)}: expected [B]")
+    B = seeds.shape[0]
+    sd = seed_tensor(seeds, B, seeds.device)
+    temp = None if temperature is None else per_row(temperature, B, seeds.device, "temperature")
+    z = torch.empty((B, int(C), int(T)), dtype=torch.float32, device=seeds.device)
+    check(lib().mt_noise_fill(ptr(sd), ptr(temp), B, int(C), int(T), ptr(z), stream_handle(seeds.device)),
+          "noise_fill")
+    return z
+
+
+def durations(logw: torch.Tensor, x_mask: torch.Tensor, length_scale):
+    """model.py:1273-1275 -> (w_ceil [B,1,Tx], cum [B,Tx], y_lengths int64 [B]). length_scale: a number, or one
+    per utterance ([B] tensor or sequence; mt_durations_scaled)."""
     require_gpu(logw, x_mask, what="durations")
     logw, x_mask = f32c(logw), f32c(x_mask)
     B, _, Tx = logw.shape
     w_ceil = torch.empty((B, 1, Tx), dtype=torch.float32, device=logw.device)
     cum = torch.empty((B, Tx), dtype=torch.float32, device=logw.device)
     yl = torch.empty((B,), dtype=torch.int64, device=logw.device)
+    if not is_scalar(length_scale):
+        ls = per_row(length_scale, B, logw.device, "length_scale")
+        check(lib().mt_durations_scaled(ptr(logw), ptr(x_mask), ptr(ls), B, Tx, ptr(w_ceil), ptr(cum), ptr(yl),
+                                        stream_handle(logw.device)), "durations_scaled")
+        return w_ceil, cum, yl
     check(lib().mt_durations(ptr(logw), ptr(x_mask), float(length_scale), B, Tx, ptr(w_ceil), ptr(cum),
                              ptr(yl), stream_handle(logw.device)), "durations")
     return w_ceil, cum, yl

@@ -434,14 +434,25 @@ class BASECFM(nn.Module):
         self.estimator = None
 
     @torch.inference_mode()
-    def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, max_valid=None):
+    def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, max_valid=None, seeds=None):
         """z = randn_like(mu)*temperature, then the Euler/midpoint loop — one HIP call. max_valid (extension, not
         in the reference signature): the most valid frames of any utterance when the caller knows it (synthesize's
-        y_max); it lets the solver prove every utterance padded and use the query-independent attention."""
+        y_max); it lets the solver prove every utterance padded and use the query-independent attention.
+        temperature (extension): a number, or one value per utterance ([B] tensor or sequence). seeds (extension):
+        int64 [B] tensor or B ints; utterance b then starts from the seeded stream of seeds[b] (rt.seeded_noise),
+        which depends on neither the batch nor the padded length, drawn inside the solve."""
         rt.require_gpu(mu, mask, spks, what="CFM.forward")
         mu, mask, spks = rt.f32c(mu), rt.f32c(mask), rt.f32c(spks)
-        z = torch.randn_like(mu)
         est = self.estimator
+        if seeds is not None:
+            return est.engine().solve(est.packed(mu.device), None, temperature, mu, mask, spks, int(n_timesteps),
+                                      self.solver, max_valid=int(max_valid or 0), seeds=seeds)
+        if not rt.is_scalar(temperature):
+            # unseeded, one temperature per utterance: the same draw, scaled per row here
+            z = torch.randn_like(mu) * rt.per_row(temperature, mu.shape[0], mu.device, "temperature")[:, None, None]
+            return est.engine().solve(est.packed(mu.device), z, 1.0, mu, mask, spks, int(n_timesteps), self.solver,
+                                      out=z, max_valid=int(max_valid or 0))
+        z = torch.randn_like(mu)
         return est.engine().solve(est.packed(mu.device), z, temperature, mu, mask, spks, int(n_timesteps),
                                   self.solver, out=z, max_valid=int(max_valid or 0))
 
@@ -514,9 +525,19 @@ class MatchaTTS(nn.Module):
                                   "path, train_standalone.py:580-707); MatchaTTS.forward is a placeholder upstream")
 
     @torch.inference_mode()
-    def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0):
-        """model.py:1264-1300 -> (mel [B,80,y_max], y_lengths int64 [B], attn [B,1,Tx,T_pad])."""
+    def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None):
+        """model.py:1264-1300 -> (mel [B,80,y_max], y_lengths int64 [B], attn [B,1,Tx,T_pad]).
+        Extensions for mixed batches: temperature and length_scale each take a number or one value per utterance
+        ([B] tensor or sequence); seeds (int64 [B] tensor or B ints) gives utterance b the noise of seeds[b], the
+        same whatever its position, the batch, the padded length or the device (rt.seeded_noise; None: randn_like)."""
         rt.require_gpu(x, x_lengths, spks, what="MatchaTTS.synthesize")
+        B = x.shape[0]
+        if seeds is not None:
+            seeds = rt.seed_tensor(seeds, B, x.device)
+        if not rt.is_scalar(temperature):
+            temperature = rt.per_row(temperature, B, x.device, "temperature")
+        if not rt.is_scalar(length_scale):
+            length_scale = rt.per_row(length_scale, B, x.device, "length_scale")
         mu, logw, x_mask, oov = self.encoder.forward_unchecked(x, x_lengths, spks)
         w_ceil, cum, y_lengths = rt.durations(logw, x_mask, length_scale)
         # validate the estimator's packed weights now, while the GPU runs the encoder, instead of after the
@@ -532,18 +553,18 @@ class MatchaTTS(nn.Module):
                 raise IndexError("index out of range in self (a token id of x lies outside [0, n_vocab))")
             t_pad = fix_len_compatibility(y_max)
             attn, mu_y, y_mask = rt.alignment(cum, y_lengths, t_pad, mu)
-            z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max)
+            z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max, seeds=seeds)
         finally:
             est._pk.untrust()
         mel = rt.denorm_crop(z, self.mel_mean, self.mel_std, y_max)
         return mel, y_lengths, attn
 
     @torch.inference_mode()
-    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0):
+    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None):
         """Upstream-Matcha-style alias (notebooks: MOS_audiou_generator.ipynb:294) -> dict."""
         import time
         t0 = time.perf_counter()
-        mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale)
+        mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale, seeds)
         y_max = mel.shape[-1]
         dt = time.perf_counter() - t0
         return {"mel": mel, "mel_lengths": y_lengths, "attn": attn[:, :, :, :y_max],
