@@ -92,6 +92,9 @@ int mt_encoder_set_vconv(mt_encoder* e, int enable);
  * parts reach 2^-16, accumulated in fp32 (the reference's fp32 to a few ulp, at 16x the fp32 MFMA rate per product);
  * 0 (default) = exact fp32 MFMA. Not a bf16 encoder: its logw stays within 1e-5 of the fp32 reference. */
 int mt_encoder_set_split(mt_encoder* e, int enable);
+/* Store policy of the mt_vconv launches' 16-byte output stores: 0 plain (default), 1 write-through (sc1); same bits.
+ * Any other mode is refused. */
+int mt_encoder_set_store_policy(mt_encoder* e, int mode);
 /* oov (nullable, device int32): set to 0, then to 1 when any id of x (padding included) lies outside [0, n_vocab):
  * nn.Embedding's IndexError (model.py:522); the caller raises at its next host sync. The embedding reads a clamped
  * row for such an id, so the launch itself stays in bounds. */
@@ -211,6 +214,11 @@ int mt_vocoder_set_vconv(mt_vocoder* v, int mode);
  * 32-channel stages' pairs and the 128-channel stage's k = 3 resblock; 4: every 128-channel pair too; 2: none of
  * the 128-channel stage; 0: every pair as two per-layer launches. Same bits in every mode. */
 int mt_vocoder_set_pair(mt_vocoder* v, int enable);
+/* Store policy of the bf16 stages' 16-byte output stores: bit i of stage_mask = stage i's launches (its upsampler and
+ * its ResBlock convs / pairs) store write-through (sc1: the line leaves the XCD's L2 at once instead of at the launch
+ * boundary); 0 = plain stores everywhere (default). Same bits either way. A mask naming a stage the vocoder does not
+ * have is refused. */
+int mt_vocoder_set_store_policy(mt_vocoder* v, int stage_mask);
 int mt_vocoder_pack(const mt_vocoder* v, const float* const* params, void* packed, void* stream);
 size_t mt_vocoder_workspace_bytes(const mt_vocoder* v, int B, int T);
 /* mel [B,80,T] fp32 -> wav [B,1,T*prod(up_rates)] fp32 */
@@ -430,8 +438,10 @@ int mt_ffn_set_min_frames(int frames);
  * padding) computed in the first estimator evaluation of a mt_cfm_solve only and kept per transformer block for the
  * later ones: it depends on the weights and on the number of masked frames, not on the ODE state, the time, mu or the
  * speaker, so recomputing it (two launches per block and evaluation) gives the same bits. Never kept across solves or
- * graph replays; single evaluations (mt_decoder_step) always compute it. Default 3 (MT_DECK=<mask> in the
- * environment); process-wide; returns the previous mask. */
+ * graph replays; single evaluations (mt_decoder_step) always compute it. Bits 2 (value 4) and 3 (value 8): the bf16
+ * evaluation's streaming launches at level 0 (T frames) / level 1 (T/2 frames) store their 16-byte outputs
+ * write-through (sc1) instead of plain (level 0 only while its activations fit the L2); same bits. Default 15
+ * (MT_DECK=<mask> in the environment); process-wide; bits past 15 are ignored; returns the previous mask. */
 int mt_decoder_set_kernels(int mask);
 /* qkv [B][T][3*heads*64], mask [B][T] -> out [B][T][heads*64], reference mask semantics */
 int mt_op_attention(int dtype, const void* qkv, const float* mask, void* out, int B, int T, int heads,

@@ -461,7 +461,9 @@ __global__ __launch_bounds__(256) void attn_uni_vec_kernel(int SP, const float* 
   }
 }
 
-// x += o_b on every frame of the slice, + the next LayerNorm's per-slab (mean, M2) (grid slices x B)
+// x += o_b on every frame of the slice, + the next LayerNorm's per-slab (mean, M2) (grid slices x B); STP: the store
+// policy of the x store (mt_common.h; the 8-byte statistics stay plain)
+template <int STP>
 __global__ __launch_bounds__(256) void attn_uni_apply_kernel(bf16* __restrict__ x, int T, const float* __restrict__ ovec,
                                                              float* __restrict__ row_out, int xr) {
   __shared__ float ob[UNI_C];
@@ -494,7 +496,10 @@ __global__ __launch_bounds__(256) void attn_uni_apply_kernel(bf16* __restrict__ 
         v[2 * e + 1] = (float)hi;
         w[e] = (uint32_t)__builtin_bit_cast(uint16_t, lo) | ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16);
       }
-      *reinterpret_cast<u32x4*>(x + ((size_t)b * T + j) * UNI_C + c) = w;
+      if constexpr (STP != ST_PLAIN)  // the same store through the utterance's [T][256] rows as a buffer
+        buf_store16<STP>(w, buf_rsrc(x + (size_t)b * T * UNI_C, (unsigned)T * (UNI_C * 2u)), (unsigned)((j * UNI_C + c) * 2));
+      else
+        *reinterpret_cast<u32x4*>(x + ((size_t)b * T + j) * UNI_C + c) = w;
       // (mean, M2) of the 64-channel slab (8 lanes x 8 channels), two-pass over the stored values
       float sm = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 #pragma unroll
@@ -542,7 +547,10 @@ int launch_uniform_apply(void* x, int B, int T, const float* ovec, float* row_ou
   MT_REQUIRE(x && ovec && row_out && B > 0 && T > 0, "uniform attention apply: arguments");
   const int SP = uniform_part_slices(T);
   const int xr = xcd_remap_for((size_t)B * T * UNI_C * sizeof(bf16));
-  hipLaunchKernelGGL(attn_uni_apply_kernel, dim3(SP, B), dim3(256), 0, st, (bf16*)x, T, ovec, row_out, xr);
+  // the store policy (mt_common.h); its buffer store addresses an utterance with 32-bit byte offsets
+  const bool wt = store_policy() == ST_WT && (long long)T * UNI_C * 2 < (1ll << 31);
+  const auto kern = wt ? attn_uni_apply_kernel<ST_WT> : attn_uni_apply_kernel<ST_PLAIN>;
+  hipLaunchKernelGGL(kern, dim3(SP, B), dim3(256), 0, st, (bf16*)x, T, ovec, row_out, xr);
   MT_CHECK_HIP(hipGetLastError());
   uniform_log(UNI_LOG_APPLY, SP * B, B, T);
   return 0;

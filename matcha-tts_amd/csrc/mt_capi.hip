@@ -112,6 +112,12 @@ int mt_encoder_set_vconv(mt_encoder* e, int enable) {
   e->e.f32vc = enable ? 1 : 0;
   return 0;
 }
+int mt_encoder_set_store_policy(mt_encoder* e, int mode) {
+  MT_REQUIRE(e, "null encoder");
+  MT_REQUIRE(mode == 0 || mode == 1, "encoder_set_store_policy: mode %d (0 plain, 1 write-through)", mode);
+  e->e.wt = mode;
+  return 0;
+}
 int mt_encoder_set_split(mt_encoder* e, int enable) {
   MT_REQUIRE(e, "null encoder");
   MT_REQUIRE(!enable || e->e.dtype == mt::F32, "encoder_set_split: the split-bf16 FFN is an fp32-encoder mode");
@@ -273,6 +279,14 @@ int mt_vocoder_set_vconv(mt_vocoder* v, int enable) {
 int mt_vocoder_set_pair(mt_vocoder* v, int enable) {
   MT_REQUIRE(v, "null vocoder");
   v->v.pair = enable < 0 ? 0 : enable;
+  return 0;
+}
+int mt_vocoder_set_store_policy(mt_vocoder* v, int stage_mask) {
+  MT_REQUIRE(v, "null vocoder");
+  const int n = (int)v->v.ups.size();
+  MT_REQUIRE(stage_mask >= 0 && stage_mask < (1 << n), "vocoder_set_store_policy: mask %d names a stage past the %d stages",
+             stage_mask, n);
+  v->v.wt_stages = stage_mask;
   return 0;
 }
 size_t mt_vocoder_packed_bytes(const mt_vocoder* v) { return v ? v->v.packed_bytes : 0; }

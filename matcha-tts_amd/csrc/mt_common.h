@@ -125,6 +125,33 @@ __device__ __forceinline__ void buf_lds16(__amdgpu_buffer_rsrc_t r, unsigned vof
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
 }
 
+// Store policy of the streaming kernels' 16-byte output stores: the `aux` immediate of their buffer stores, fixed at
+// compile time per instantiation. ST_PLAIN keeps the written line in the XCD's L2 (dirty until the kernel ends, when
+// the launch boundary writes it back); ST_WT (sc1, write-through) sends it on at once and drops the line, so the
+// boundary finds less to write back and a same-XCD consumer reads the line from the Infinity Cache. Same values at
+// the same addresses either way; visibility still comes from the kernel boundary, never from the policy. Stores
+// narrower than 16 bytes per lane (statistics, o_b slots, waveforms) stay plain.
+enum : int { ST_PLAIN = 0, ST_WT = 16 };
+// The policy the launch_* functions of the kernels above instantiate with: a host-side value the engines (decoder
+// per level, encoder, vocoder per stage) set around their launches; 0 outside an engine's scope.
+int store_policy();
+struct StorePolicyScope {
+  explicit StorePolicyScope(int policy);
+  ~StorePolicyScope();
+  void set(int policy);
+  StorePolicyScope(const StorePolicyScope&) = delete;
+  StorePolicyScope& operator=(const StorePolicyScope&) = delete;
+
+ private:
+  int prev_;
+};
+// 16 bytes of this lane to base + voff of a raw buffer resource under policy SP (an offset past the range: dropped)
+template <int SP>
+__device__ __forceinline__ void buf_store16(u32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff) {
+  static_assert(SP == ST_PLAIN || SP == ST_WT, "store policy");
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, 0, SP);
+}
+
 // bf16 epilogue helpers: two channels of one packed word as packed fp32 math (v_pk_add_f32 / v_pk_mul_f32), one
 // v_cvt_pk_bf16_f32 (RNE) per word, lrelu as max(x, slope * x) — equal to x > 0 ? x : slope * x for every non-NaN
 // x when 0 <= slope <= 1 (files using it build with -mno-amdgpu-ieee so the max needs no NaN canonicalize)

@@ -496,7 +496,7 @@ __global__ __launch_bounds__(TL::NT) void conv_kernel(ConvArgs a) {
 constexpr int PJ_C = 256;
 constexpr int PJ_ROW = PJ_C * 2 + 16;  // LDS row bytes: a fragment's 16 rows hit 16 distinct 16-byte bank slots
 
-template <int MB>  // n_feats = 16 * MB
+template <int MB, int SP = ST_PLAIN>  // n_feats = 16 * MB; SP: the store policy of the 16-byte z master store (mt_common.h)
 __global__ __launch_bounds__(256) void proj_euler_kernel(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) char wl[16 * MB * PJ_ROW];
   __shared__ float ga[PJ_C], gsh[PJ_C], lnm[8], lnr[8];
@@ -611,8 +611,15 @@ __global__ __launch_bounds__(256) void proj_euler_kernel(ConvArgs a) {
       zn4[r] = zn;
       o[r] = (bf16)(zn * em);  // the estimator-input slot is read as x * mask only
     }
-    if (a.update_master) *reinterpret_cast<f32x4*>(zp) = zn4;
-    *reinterpret_cast<bf16x4*>(xz) = o;
+    if (a.update_master) {
+      if constexpr (SP != ST_PLAIN)  // the same store through the utterance's fp32 [T][80] master rows as a buffer
+        buf_store16<SP>(__builtin_bit_cast(u32x4, zn4),
+                        buf_rsrc(a.zmaster + (size_t)b * a.Tout * a.cout, (unsigned)a.Tout * (unsigned)a.cout * 4u),
+                        (unsigned)((f * a.cout + ch) * 4));
+      else
+        *reinterpret_cast<f32x4*>(zp) = zn4;
+    }
+    *reinterpret_cast<bf16x4*>(xz) = o;  // 8 bytes per lane: plain under every policy
   }
 }
 
@@ -628,7 +635,10 @@ int launch_proj_euler(const ConvArgs& a, hipStream_t stream) {
              "proj_euler: null pointer");
   MT_REQUIRE((reinterpret_cast<uintptr_t>(a.zmaster) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.xin_z) & 7) == 0,
              "proj_euler: z / estimator-input alignment");
-  hipLaunchKernelGGL(proj_euler_kernel<5>, dim3((unsigned)((a.Tin + 63) / 64), (unsigned)a.B), dim3(256), 0, stream, a);
+  // the store policy (mt_common.h); its buffer store addresses an utterance's master rows with 32-bit byte offsets
+  const bool wt = store_policy() == ST_WT && (long long)a.Tout * a.cout * 4 < (1ll << 31);
+  const auto kern = wt ? proj_euler_kernel<5, ST_WT> : proj_euler_kernel<5>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((a.Tin + 63) / 64), (unsigned)a.B), dim3(256), 0, stream, a);
   MT_CHECK_HIP(hipGetLastError());
   // launch log (tests/test_gpu_decoder_kernels.py: the dedicated kernel, not the generic conv, ran): tag 0x20000
   const int rec[VCLOG_FIELDS] = {0x20000, 80, 64, 1, (a.Tin + 63) / 64 * a.B, (a.Tin + 63) / 64 * a.B, 1, 80, PJ_C,

@@ -27,7 +27,7 @@ static int g_deck = -1;
 int dec_kernels() {
   if (g_deck < 0) {
     const char* e = getenv("MT_DECK");
-    g_deck = e ? atoi(e) & DECK_ALL : DECK_ALL;
+    g_deck = e ? atoi(e) & DECK_ALL : DECK_DEFAULT;
   }
   return g_deck;
 }
@@ -745,7 +745,12 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
   // DECK_OVEC: transformer block j of resnet r keeps its o_b in slot (blocks before resnet r) + j of w.uvec;
   // evaluation 0 of the chain (and a single evaluation: step, step_times) computes it, the later ones read it
   const bool ovk = std::is_same<E, bf16>::value && (dec_kernels() & DECK_OVEC);
-  auto tblocks = [&](int r, void* x, const float* m, int Tl) -> int {
+  // DECK_WT0 / DECK_WT1: the store policy of this evaluation's launches, by the level whose frames they write (the
+  // down conv writes level 1, the up conv level 0)
+  const bool l0fits = (size_t)B * T * C * sizeof(bf16) <= kDeckWt0MaxBytes;
+  const int wt0 = (dec_kernels() & DECK_WT0) && l0fits ? ST_WT : ST_PLAIN, wt1 = (dec_kernels() & DECK_WT1) ? ST_WT : ST_PLAIN;
+  StorePolicyScope pol(wt0);
+  auto tblocks =[&](int r, void* x, const float* m, int Tl) -> int {
     const int nb = (int)tbs[r].size();
     const bool uni = uniform_attn && (Tl == T ? w.uni0 : w.uni1);
     size_t slot = 0;
@@ -780,6 +785,7 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
   if ((rc = tap(w, 0, w.H0, B, T, st))) return rc;
   if ((rc = tblocks(0, w.H0, m0, T))) return rc;
   if ((rc = tap(w, 1, w.H0, B, T, st))) return rc;
+  pol.set(wt1);
   if (mio && vc(down0)) {  // frame pairs: [T][C] rows read as [T/2][2C]
     VConvArgs a = vargs(down0, P, w, w.H0, B, T1, w.XA);
     a.taps = 2;
@@ -810,6 +816,7 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
     if ((rc = resnet<E>(P, w, res[r], half[cur], w.H1, C, 2 * C, mio, half[nx], m1, B, T1, tbp(r), &rs, st)))
       return rc;
     if ((rc = tblocks(r, half[nx], m1, T1))) return rc;
+    pol.set(wt0);
     if (mio && vc(up0)) {  // ConvTranspose1d k4 s2 p1 -> T as a polyphase conv with a placed, masked output
       int Tout = 0, Ncols = 0;
       gemm_geom(up0, T1, &Tout, &Ncols);

@@ -696,6 +696,7 @@ template <class E>
 int Encoder::forward_t(const char* P, const long long* ids, const long long* xlen, const float* spks, int B, int Tx,
                        float* mu, float* logw, float* xmask, int* oov, char* ws, hipStream_t st) const {
   int rc;
+  StorePolicyScope pol(wt ? ST_WT : ST_PLAIN);  // the mt_vconv launches' store policy (wt, mt_model.h)
   const size_t n = (size_t)B * Tx;
   const int wmax = std::max(std::max(W, 3 * W), std::max(F, DF));
   const size_t big = align256(n * wmax * esize);

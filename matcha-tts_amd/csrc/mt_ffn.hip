@@ -68,7 +68,7 @@ __device__ __forceinline__ void ff_for(F&& f) {
   }
 }
 
-template <bool MASK, bool OVL, bool UNI, bool PFB = false>
+template <bool MASK, bool OVL, bool UNI, bool PFB = false, int SP = ST_PLAIN>  // SP: the output store's policy (mt_common.h)
 __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[FLDS];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -360,6 +360,13 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
           swap16(o1[0][0], o1[1][0]);
           swap16(o1[0][1], o1[1][1]);
           const int n = n0 + row;
+          if constexpr (SP != ST_PLAIN) {
+            // the same store through the [NF][256] rows as a buffer: a frame past NF gets an offset past any range and
+            // is dropped instead of landing on the trash line; every lane still stores
+            const unsigned vo = n < NF ? (unsigned)((n * FC + ch * 128 + fp * 32 + ch16) * 2) : 0x80000000u;
+            buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, buf_rsrc(a.x, (unsigned)NF * (FC * 2u)), vo);
+            continue;
+          }
           const size_t off = (size_t)n * FC + ch * 128 + fp * 32 + ch16;
           *reinterpret_cast<u32x4*>(n < NF ? a.x + off : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
         }
@@ -654,7 +661,13 @@ int launch_ffn(const FfnArgs& a, hipStream_t st) {
   MT_REQUIRE(!a.ovec || a.T > 0, "ffn: ovec needs T");
   const int mode = ffn_knob();  // 1 serial, 2 overlapped FF1 epilogues, 3 serial with frame-only prefetch
   void (*kern)(FfnArgs);
-  if (mode == 2)
+  // the store policy (mt_common.h) exists on the default schedule (3); the A/B schedules 1 and 2 store plain. Its
+  // buffer store addresses the [frames][256] rows with 32-bit byte offsets
+  const bool wt = store_policy() == ST_WT && (long long)a.frames * FC * 2 < (1ll << 31);
+  if (mode == 3 && wt)
+    kern = a.ovec ? (a.emask ? ffn_kernel<true, false, true, true, ST_WT> : ffn_kernel<false, false, true, true, ST_WT>)
+                  : (a.emask ? ffn_kernel<true, false, false, true, ST_WT> : ffn_kernel<false, false, false, true, ST_WT>);
+  else if (mode == 2)
     kern = a.ovec ? (a.emask ? ffn_kernel<true, true, true> : ffn_kernel<false, true, true>)
                   : (a.emask ? ffn_kernel<true, true, false> : ffn_kernel<false, true, false>);
   else if (mode == 3)

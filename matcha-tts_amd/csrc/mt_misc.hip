@@ -565,6 +565,7 @@ int mask_rows(int dtype, void* x, int rows, int C, const float* mask, hipStream_
 
 // one block = GN_FR frames of one utterance; C/8 threads x 8 channels (16 B) per frame row
 constexpr int GN_FR = 32;
+template <int SP>  // SP: the output store's policy (mt_common.h)
 __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16* __restrict__ y, int T, int C,
                                                        const double* __restrict__ part, int nparts,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -640,14 +641,20 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16* __restrict__ 
       const bf16 h0 = (bf16)r0, h1 = (bf16)r1;
       o[e] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
     }
-    *reinterpret_cast<u32x4*>(h + row * C + c) = o;
+    if constexpr (SP != ST_PLAIN)  // the same store through the utterance's [T][C] rows as a buffer
+      buf_store16<SP>(o, buf_rsrc(h + (size_t)b * T * C, (unsigned)T * (unsigned)C * 2u), (unsigned)((t * C + c) * 2));
+    else
+      *reinterpret_cast<u32x4*>(h + row * C + c) = o;
   }
 }
 
 int gn_apply(const void* y, int B, int T, int C, const double* part, int nparts, const float* gamma,
              const float* beta, float eps, const float* tb, int tb_ld, const float* mask, void* h, hipStream_t st) {
   MT_REQUIRE(C % 32 == 0 && C <= 256 && C >= 64 && 256 % (C / 8) == 0 && nparts > 0, "gn_apply: C %d", C);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3((T + GN_FR - 1) / GN_FR, B), dim3(256), 0, st, (const bf16*)y, T, C, part, nparts,
+  // the store policy (mt_common.h); its buffer store addresses an utterance with 32-bit byte offsets
+  const bool wt = store_policy() == ST_WT && (long long)T * C * 2 < (1ll << 31);
+  const auto kern = wt ? gn_apply_kernel<ST_WT> : gn_apply_kernel<ST_PLAIN>;
+  hipLaunchKernelGGL(kern, dim3((T + GN_FR - 1) / GN_FR, B), dim3(256), 0, st, (const bf16*)y, T, C, part, nparts,
                      gamma, beta, eps, tb, tb_ld, mask, (bf16*)h, xcd_remap_for((size_t)B * T * C * sizeof(bf16)));
   MT_CHECK_HIP(hipGetLastError());
   return 0;

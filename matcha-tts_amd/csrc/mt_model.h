@@ -61,9 +61,14 @@ size_t align256(size_t x);
 // Decoder kernel variants, each bit-identical to the launches it replaces (mt_decoder_set_kernels): DECK_PROJ the
 // final projection + ODE update on proj_euler_kernel (mt_conv.hip) instead of the generic conv kernel; DECK_OVEC the
 // query-independent attention's o_b computed in the first evaluation of a solve only and kept per transformer block
-// for the later ones (it does not depend on the ODE state), instead of two launches per block and evaluation. On by
-// default; MT_DECK=<mask> in the environment (read once) or dec_set_kernels() to change.
-enum : int { DECK_PROJ = 1, DECK_OVEC = 2, DECK_ALL = 3 };
+// for the later ones (it does not depend on the ODE state), instead of two launches per block and evaluation. Both on
+// by default; MT_DECK=<mask> in the environment (read once) or dec_set_kernels() to change.
+// DECK_WT0 / DECK_WT1: the write-through store policy (ST_WT, mt_common.h) on the bf16 evaluation's streaming
+// launches at level 0 (T frames) / level 1 (T/2 frames); same bits; both on by default (DESIGN "Store policy").
+// Level 0 takes it only while its [B][T][256] bf16 activations fit the 32 MiB of L2 (kDeckWt0MaxBytes): measured a
+// gain at B = 32 (12 MB) and a loss at B = 256 (99 MB); level 1 gained at both.
+enum : int { DECK_PROJ = 1, DECK_OVEC = 2, DECK_WT0 = 4, DECK_WT1 = 8, DECK_ALL = 15, DECK_DEFAULT = DECK_ALL };
+constexpr size_t kDeckWt0MaxBytes = (size_t)32 << 20;
 int dec_kernels();
 int dec_set_kernels(int mask);  // -> the previous mask
 
@@ -199,6 +204,8 @@ struct Encoder {
   int f32vc = 1;      // fp32: convs on mt_vconv's fp32 mode (1, default) or the generic conv kernel (0; A/B, tests)
   int split = 0;      // fp32: the FFN convs on mt_vconv's split-bf16 mode (VConvArgs::f32 == 2; encoder precision
                       // "fp32x3": fp32-level products on the bf16 MFMA pipe) instead of exact fp32 MFMA
+  int wt = 0;         // 1: the mt_vconv launches store under the write-through policy (ST_WT, mt_common.h); same bits;
+                      // off by default (DESIGN "Store policy")
   ParamList params;
   size_t packed_bytes = 0;
   int emb = -1;
@@ -248,6 +255,10 @@ struct Vocoder {
   // the 128-, 64- and 32-channel stages' ResBlock pairs as one launch each (mt_vpair128 / mt_vpair / mt_vpair32;
   // needs vconv >= 2). The 128-channel stage: 1 = its k = 3 resblock fused, 4 = all fused, 2 = none (per layer)
   int pair = 1;
+  // bit i: stage i's launches (its upsampler and its ResBlock convs / pairs) store under the write-through policy
+  // (ST_WT, mt_common.h); same bits either way. kDefaultWt: the stages the A/B measured a gain on (DESIGN "Store policy")
+  static constexpr int kDefaultWt = 0;
+  int wt_stages = kDefaultWt;
   size_t zero_off = 0;  // 256 zero bytes in the packed buffer (vconv padding rows)
   bool any_vc = false;
   std::vector<int> up_rates, up_kernels, rb_kernels;

@@ -116,8 +116,9 @@ __device__ __forceinline__ void rb_for(F&& f) {
   }
 }
 
-template <int EF, int C, int K, int LW>
+template <int EF, int C, int K, int LW, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
+  static_assert(SP == ST_PLAIN || (RB_BUF & 4) != 0, "the store policy rides on the buffer stores");
   constexpr int WPW = RbStage<LW>::WPW, XPW = RbStage<LW>::XPW, TX = rb_tx<K, LW>();
   constexpr bool ACTIN = (EF & VE_ACTIN) != 0;
   using SCH = VcSched<C / 64, K, RNW, 2, TX, WPW, XPW, rb_nst<EF>(), ACTIN ? 2 : 1>;
@@ -334,11 +335,11 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
           // lane still issues its store, so the counted waits' NST is unchanged
           const unsigned vo = (unsigned)((n * C + ch16 + fp * 32) * 2);
           if constexpr ((EF & VE_Y2ONLY) == 0)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo, 0, 0);
+            buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
           if constexpr ((EF & VE_DUAL) != 0 && (RB_EXP & 2) == 0) {
             swap16(o2[0][0], o2[1][0]);
             swap16(o2[0][1], o2[1][1]);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo, 0, 0);
+            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
           }
           continue;
         }
@@ -543,7 +544,10 @@ void rb_launch(int G, const VConvArgs& a, hipStream_t st) {
   using SCH = VcSched<C / 64, K, RNW, 2, TX, WPW, XPW, rb_nst<EF>(), ACTIN ? 2 : 1>;
   (void)SchedReg<1, C / 64, K, RNW, 2, TX, WPW, XPW, rb_nst<EF>(), ACTIN ? 2 : 1,
                  ACTIN ? 0 : SCH::wait_first(-1)>::reg;
-  hipLaunchKernelGGL((rbconv_kernel<EF, C, K, RB_LOADERS>), dim3(G), dim3(RNT), 0, st, a);
+  if (store_policy() == ST_WT)  // the store policy (mt_common.h): same schedule, same store count
+    hipLaunchKernelGGL((rbconv_kernel<EF, C, K, RB_LOADERS, ST_WT>), dim3(G), dim3(RNT), 0, st, a);
+  else
+    hipLaunchKernelGGL((rbconv_kernel<EF, C, K, RB_LOADERS>), dim3(G), dim3(RNT), 0, st, a);
 }
 // on by default; MT_RBCONV=0 in the environment or mt_vconv_set_rbconv(0): the generic mt_vconv kernel instead
 int g_rb = -1;

@@ -40,6 +40,9 @@ enum : int {
   VE_SPLIT6 = 65536, // split-bf16 mode (VConvArgs::f32 == 2) only: the fp32 result is stored as its 3-way bf16 split
                      // h1 + h2 + h3 in the 6-plane layout [frames][6 M] = (h1, h1, h1, h2, h2, h3), the next split conv's
                      // input
+  VE_WT = 262144,    // not an epilogue: launch_vconv adds it to the kernel's template flags under the write-through
+                     // store policy (ST_WT, mt_common.h); the 16-byte y / y2 stores then go through a buffer resource
+                     // with the sc1 bit. Callers never pass it, and the launch log records the epilogue without it
   VE_GNRES = 8192,   // 1x1 only, with VE_RESID: the residual is the RAW input of a GroupNorm(M/32) + Mish + mask,
                      // applied here: resid := bf16(mish(GN(resid)) * emask[frame]) with the statistics merged
                      // per tile from the producer's VE_GNSTATS partials (ResnetBlock1D block2 -> + res(x),

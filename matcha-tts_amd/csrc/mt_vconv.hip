@@ -138,8 +138,39 @@ struct CtSched {
 // v_mfma_f32_16x16x4_f32 (mfma16), and the epilogue stores fp32 in the accumulator layout (bias, ReLU, residual, mask
 // only). FM 2, split-bf16 (VConvArgs::f32 == 2): the bf16 K loop over the 6-plane operands with FM 1's fp32 epilogue
 // (or, VE_SPLIT6, the 6-plane split of its result).
-template <int EF, int BMT, bool K1, int BNT = BN, int FM = 0, int CTN = 0, int CTT = 0>
+// Instantiations (EF, BMT, K1, BNT, FM, CTN, CTT) whose write-through form spills more registers than their plain form
+// (tools/kernel_regs.py compares the two from the code object's metadata; DESIGN "Store policy"): they store plain
+// under VE_WT as well. Regenerate after a change to the kernel: register allocation moves with it.
+struct VcWtKey {
+  int ef, bm, k1, bn, fm, n, t;
+};
+constexpr VcWtKey kVcWtPlain[] = {
+    {1, 64, 0, 384, 0, 0, 0}, {3, 64, 0, 384, 0, 0, 0}, {3, 128, 0, 256, 0, 0, 0}, {5, 64, 0, 384, 0, 0, 0},
+    {5, 128, 0, 256, 0, 0, 0}, {7, 64, 0, 384, 0, 0, 0}, {7, 128, 0, 256, 0, 0, 0}, {16, 64, 0, 384, 0, 0, 0},
+    {16, 128, 0, 256, 0, 4, 2}, {16, 128, 0, 256, 0, 8, 2}, {17, 64, 0, 384, 0, 0, 0}, {21, 64, 0, 384, 0, 0, 0},
+    {21, 128, 0, 256, 0, 0, 0}, {23, 64, 0, 384, 0, 0, 0}, {23, 128, 0, 256, 0, 0, 0}, {128, 128, 0, 128, 0, 3, 3},
+    {128, 128, 0, 192, 0, 3, 3}, {128, 128, 0, 192, 0, 4, 3}, {128, 128, 0, 192, 0, 8, 2}, {128, 128, 0, 192, 0, 8, 3},
+    {128, 128, 0, 256, 0, 0, 0}, {128, 128, 0, 256, 0, 3, 3}, {129, 64, 0, 384, 0, 0, 0}, {129, 64, 0, 384, 2, 0, 0},
+    {129, 128, 0, 256, 0, 0, 0}, {129, 128, 0, 256, 1, 0, 0}, {129, 128, 0, 256, 2, 0, 0}, {129, 128, 1, 192, 0, 16, 1},
+    {129, 128, 1, 256, 0, 16, 1}, {256, 64, 0, 384, 0, 0, 0}, {256, 128, 0, 128, 0, 3, 3}, {256, 128, 0, 128, 0, 8, 2},
+    {256, 128, 0, 128, 0, 8, 3}, {256, 128, 0, 192, 0, 0, 0}, {256, 128, 0, 192, 0, 8, 2}, {256, 128, 0, 192, 0, 8, 3},
+    {256, 128, 0, 256, 0, 0, 0}, {256, 128, 0, 256, 0, 3, 3}, {256, 128, 0, 256, 0, 8, 2}, {256, 128, 0, 256, 0, 8, 3},
+    {513, 128, 1, 192, 0, 16, 1}, {513, 128, 1, 256, 0, 16, 1}, {1056, 128, 1, 128, 0, 4, 1}, {1056, 128, 1, 256, 0, 4, 1},
+    {1120, 128, 1, 128, 0, 4, 1}, {1120, 128, 1, 256, 0, 4, 1}, {2176, 128, 0, 256, 0, 0, 0}, {4096, 64, 0, 384, 0, 0, 0},
+    {8705, 64, 1, 128, 0, 0, 0}, {8705, 128, 1, 128, 0, 3, 1}, {8705, 128, 1, 192, 0, 4, 1}, {8705, 128, 1, 192, 0, 8, 1},
+    {8705, 128, 1, 256, 0, 4, 1}, {8705, 128, 1, 256, 0, 8, 1}, {67712, 128, 0, 256, 2, 0, 0},
+};
+constexpr bool vc_wt_plain(int ef, int bm, bool k1, int bn, int fm, int n, int t) {
+  for (const VcWtKey& k : kVcWtPlain)
+    if (k.ef == ef && k.bm == bm && k.k1 == (int)k1 && k.bn == bn && k.fm == fm && k.n == n && k.t == t) return true;
+  return false;
+}
+
+// EFT: the epilogue flags EF, plus VE_WT for the write-through store policy (SP; the launchers add it).
+template <int EFT, int BMT, bool K1, int BNT = BN, int FM = 0, int CTN = 0, int CTT = 0>
 __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
+  constexpr int EF = EFT & ~VE_WT;
+  constexpr int SP = (EFT & VE_WT) && !vc_wt_plain(EF, BMT, K1, BNT, FM, CTN, CTT) ? ST_WT : ST_PLAIN;
   constexpr bool F32 = FM == 1;   // fp32 K loop (operands, fragments, MFMA)
   constexpr bool F32E = FM != 0;  // fp32 epilogue (fp32 residual; fp32 output unless VE_SPLIT6)
   using TT = VT<BMT, K1, vc_npar<EF>(), BNT>;
@@ -379,6 +410,12 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
 #pragma unroll
           for (int pl = 0; pl < 6; ++pl) {
             const int q = pl < 3 ? 0 : pl < 5 ? 1 : 2;
+            if constexpr (SP != ST_PLAIN) {  // the same store through y as a buffer of 2 GiB (as the bf16 epilogue below)
+              const unsigned vo =
+                  n < L ? (unsigned)(((b * L + n) * (int)ld6 + m0 + ch16 + fp * 32 + pl * a.M) * 2) : 0x80000000u;
+              buf_store16<SP>(u32x4{pt[q][0][0], pt[q][0][1], pt[q][1][0], pt[q][1][1]}, buf_rsrc(a.y, 0x80000000u), vo);
+              continue;
+            }
             *reinterpret_cast<u32x4*>(n < L ? a.y + o + (size_t)pl * a.M : a.trash + 8 * lane) =
                 u32x4{pt[q][0][0], pt[q][0][1], pt[q][1][0], pt[q][1][1]};
           }
@@ -400,6 +437,11 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
             v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
           if constexpr ((EF & VE_RESID) != 0) v = v + rv32[fm][fn];
           if constexpr ((EF & VE_MASK) != 0) v = v * mk[fn];
+          if constexpr (SP != ST_PLAIN) {  // the same store through y as a buffer of 2 GiB (as the bf16 epilogue below)
+            const unsigned vo = n < L ? (unsigned)(((b * L + n) * a.M + m) * 4) : 0x80000000u;
+            buf_store16<SP>(__builtin_bit_cast(u32x4, v), buf_rsrc(a.y, 0x80000000u), vo);
+            continue;
+          }
           float* yp = reinterpret_cast<float*>(a.y) + ((size_t)b * L + n) * a.M + m;
           *reinterpret_cast<f32x4*>(n < L ? yp : reinterpret_cast<float*>(a.trash) + 4 * lane) = v;
         }
@@ -591,6 +633,19 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
         const int n = n0 + wn * WNC + fn * 16 + l16;
         const int e = n * a.ldy + m0 + ch16 + fp * 32 - a.yshift;  // element of this utterance's output
         const bool ok = n < a.Lout && e >= 0 && e < a.ylim;
+        if constexpr (SP != ST_PLAIN) {
+          // the same stores through y / y2 as buffers of 2 GiB (the launcher checks that the output ends below that): a
+          // store that is not ok gets the offset past the range and is dropped instead of landing on the trash line;
+          // every lane still stores. The descriptors are the kernel arguments plus two constants: no SGPRs per tile
+          const unsigned vo = ok ? (unsigned)(b * (int)a.ystride + e) * 2u : 0x80000000u;
+          buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, buf_rsrc(a.y, 0x80000000u), vo);
+          if constexpr ((EF & VE_DUAL) != 0) {
+            swap16(o2[0][0], o2[1][0]);
+            swap16(o2[0][1], o2[1][1]);
+            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, buf_rsrc(a.y2, 0x80000000u), vo);
+          }
+          continue;
+        }
         const size_t o = (size_t)b * a.ystride + e;
         *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
         if constexpr ((EF & VE_DUAL) != 0) {
@@ -1223,28 +1278,37 @@ static int launch_vconv_f32(int ef, const VConvArgs& a0, hipStream_t st) {
     ts_assign(a, rec);
 #endif
   }
+  // W: VE_WT under the write-through store policy (mt_common.h), else 0
 #define MT_F32CASE(E)                                                                                              \
   case E:                                                                                                          \
     if (k1) {                                                                                                      \
-      if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<E, 128, true, 256, 1>), dim3(G), dim3(NT), 0, st, a); \
-      else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, true, 128, 1>), dim3(G), dim3(NT), 0, st, a); \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, true, 128, 1>), dim3(G), dim3(NT), 0, st, a);                \
+      if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, true, 256, 1>), dim3(G), dim3(NT), 0, st, a); \
+      else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, true, 128, 1>), dim3(G), dim3(NT), 0, st, a); \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, true, 128, 1>), dim3(G), dim3(NT), 0, st, a);                \
     } else {                                                                                                       \
-      if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 256, 1>), dim3(G), dim3(NT), 0, st, a); \
-      else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 128, 1>), dim3(G), dim3(NT), 0, st, a); \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, false, 128, 1>), dim3(G), dim3(NT), 0, st, a);               \
+      if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 256, 1>), dim3(G), dim3(NT), 0, st, a); \
+      else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 128, 1>), dim3(G), dim3(NT), 0, st, a); \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, false, 128, 1>), dim3(G), dim3(NT), 0, st, a);               \
     }                                                                                                              \
     break;
-  switch (ef) {
-    MT_F32CASE(0)
-    MT_F32CASE(VE_RELU)
-    MT_F32CASE(VE_RELU | VE_MASK)
-    MT_F32CASE(VE_MASK)
-    MT_F32CASE(VE_RESID)
-    MT_F32CASE(VE_RESID | VE_MASK)
-    default: set_error("vconv f32: epilogue %d not compiled in", ef); return -1;
-  }
+  auto dispatch = [&](auto wtb) -> int {
+    constexpr int W = decltype(wtb)::value;
+    switch (ef) {
+      MT_F32CASE(0)
+      MT_F32CASE(VE_RELU)
+      MT_F32CASE(VE_RELU | VE_MASK)
+      MT_F32CASE(VE_MASK)
+      MT_F32CASE(VE_RESID)
+      MT_F32CASE(VE_RESID | VE_MASK)
+      default: set_error("vconv f32: epilogue %d not compiled in", ef); return -1;
+    }
+    return 0;
+  };
 #undef MT_F32CASE
+  // the buffer stores address the whole output with 32-bit byte offsets below 2^31; a larger one stores plain
+  const bool wt = store_policy() == ST_WT && (long long)a.B * a.L * a.M * 4 < (1ll << 31);
+  const int rc = wt ? dispatch(std::integral_constant<int, VE_WT>{}) : dispatch(std::integral_constant<int, 0>{});
+  if (rc) return rc;
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1285,16 +1349,25 @@ static int launch_vconv_split(int ef, const VConvArgs& a0, hipStream_t st) {
   }
 #define MT_SPLCASE(E)                                                                                            \
   case E:                                                                                                        \
-    if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 256, 2>), dim3(G), dim3(NT), 0, st, a); \
-    else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 128, 2>), dim3(G), dim3(NT), 0, st, a); \
-    else hipLaunchKernelGGL((vconv_kernel<E, 64, false, 384, 2>), dim3(G), dim3(NT), 0, st, a);               \
+    if (BM == 128 && bn == 256) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 256, 2>), dim3(G), dim3(NT), 0, st, a); \
+    else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 128, 2>), dim3(G), dim3(NT), 0, st, a); \
+    else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, false, 384, 2>), dim3(G), dim3(NT), 0, st, a);               \
     break;
-  switch (ef) {
-    MT_SPLCASE(VE_RELU | VE_MASK | VE_SPLIT6)
-    MT_SPLCASE(VE_RESID | VE_MASK)
-    default: set_error("vconv split: epilogue %d not compiled in", ef); return -1;
-  }
+  auto dispatch = [&](auto wtb) -> int {
+    constexpr int W = decltype(wtb)::value;  // VE_WT under the write-through store policy (mt_common.h), else 0
+    switch (ef) {
+      MT_SPLCASE(VE_RELU | VE_MASK | VE_SPLIT6)
+      MT_SPLCASE(VE_RESID | VE_MASK)
+      default: set_error("vconv split: epilogue %d not compiled in", ef); return -1;
+    }
+    return 0;
+  };
 #undef MT_SPLCASE
+  // the buffer stores address the whole output (6 bf16 planes or fp32) with 32-bit byte offsets below 2^31; a larger
+  // one stores plain
+  const bool wt = store_policy() == ST_WT && (long long)a.B * a.L * a.M * 12 < (1ll << 31);
+  const int rc = wt ? dispatch(std::integral_constant<int, VE_WT>{}) : dispatch(std::integral_constant<int, 0>{});
+  if (rc) return rc;
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1326,7 +1399,7 @@ template <int E, int BMV, bool K1V, int BNV>
 static void ct_try(const VConvArgs&, int, hipStream_t, bool&) {}
 template <int E, int BMV, bool K1V, int BNV, int N, int T, int... R>
 static void ct_try(const VConvArgs& a, int G, hipStream_t st, bool& done) {
-  (void)CtSched<E, BMV, K1V, BNV, N, T>::REG::reg;  // the schedule, for the CPU schedule test
+  (void)CtSched<E & ~VE_WT, BMV, K1V, BNV, N, T>::REG::reg;  // the schedule, for the CPU schedule test
   if (a.cin / 64 == N && a.taps == T) {
     hipLaunchKernelGGL((vconv_kernel<E, BMV, K1V, BNV, 0, N, T>), dim3(G), dim3(NT), 0, st, a);
     done = true;
@@ -1466,47 +1539,49 @@ int launch_vconv(int ef, const VConvArgs& a0, hipStream_t st) {
   if (probed) probe_begin(site, st);
 #define MT_VCASE(E)                                                                                \
   case E:                                                                                          \
-    if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, false>), dim3(G), dim3(NT), 0, st, a); \
-    else hipLaunchKernelGGL((vconv_kernel<E, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);     \
+    if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false>), dim3(G), dim3(NT), 0, st, a); \
+    else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);     \
     break;
 #define MT_VCASE_H(E)                                                                                  \
   case E:                                                                                              \
-    if (tf == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 128>), dim3(G), dim3(NT), 0, st, a); \
-    else if (tf == 192) hipLaunchKernelGGL((vconv_kernel<E, 128, false, 192>), dim3(G), dim3(NT), 0, st, a); \
-    else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, false>), dim3(G), dim3(NT), 0, st, a); \
-    else hipLaunchKernelGGL((vconv_kernel<E, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);          \
+    if (tf == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 128>), dim3(G), dim3(NT), 0, st, a); \
+    else if (tf == 192) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false, 192>), dim3(G), dim3(NT), 0, st, a); \
+    else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, false>), dim3(G), dim3(NT), 0, st, a); \
+    else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);          \
     break;
 #define MT_VCASE1(E)                                                                                    \
   case E:                                                                                               \
     if (tf1 == 128) {                                                                                   \
-      if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, true, 128>), dim3(G), dim3(NT), 0, st, a); \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, true, 128>), dim3(G), dim3(NT), 0, st, a);           \
+      if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, true, 128>), dim3(G), dim3(NT), 0, st, a); \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, true, 128>), dim3(G), dim3(NT), 0, st, a);           \
     } else if (tf1 == 192) { /* BM = 128 only (64-row tiles would give 24-frame waves) */               \
-      hipLaunchKernelGGL((vconv_kernel<E, 128, true, 192>), dim3(G), dim3(NT), 0, st, a);               \
+      hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, true, 192>), dim3(G), dim3(NT), 0, st, a);               \
     } else {                                                                                            \
-      if (BM == 128) hipLaunchKernelGGL((vconv_kernel<E, 128, true>), dim3(G), dim3(NT), 0, st, a);     \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, true>), dim3(G), dim3(NT), 0, st, a);                \
+      if (BM == 128) hipLaunchKernelGGL((vconv_kernel<(E) | W, 128, true>), dim3(G), dim3(NT), 0, st, a);     \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, true>), dim3(G), dim3(NT), 0, st, a);                \
     }                                                                                                   \
     break;
 #define MT_VCASE_HCT(E)                                                                                \
   case E:                                                                                              \
-    if (tf == 128) vlaunch<E, 128, false, 128, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                        \
-    else if (tf == 192) vlaunch<E, 128, false, 192, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                   \
-    else if (BM == 128) vlaunch<E, 128, false, BN, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                    \
-    else hipLaunchKernelGGL((vconv_kernel<E, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);          \
+    if (tf == 128) vlaunch<(E) | W, 128, false, 128, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                        \
+    else if (tf == 192) vlaunch<(E) | W, 128, false, 192, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                   \
+    else if (BM == 128) vlaunch<(E) | W, 128, false, BN, 3, 3, 4, 3, 8, 3, 8, 2>(a, G, st);                    \
+    else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);          \
     break;
 #define MT_VCASE1CT(E, ...)                                                                             \
   case E:                                                                                               \
     if (tf1 == 128) {                                                                                   \
-      if (BM == 128) vlaunch<E, 128, true, 128, __VA_ARGS__>(a, G, st);                                 \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, true, 128>), dim3(G), dim3(NT), 0, st, a);           \
+      if (BM == 128) vlaunch<(E) | W, 128, true, 128, __VA_ARGS__>(a, G, st);                                 \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, true, 128>), dim3(G), dim3(NT), 0, st, a);           \
     } else if (tf1 == 192) {                                                                            \
-      vlaunch<E, 128, true, 192, __VA_ARGS__>(a, G, st);                                                \
+      vlaunch<(E) | W, 128, true, 192, __VA_ARGS__>(a, G, st);                                                \
     } else {                                                                                            \
-      if (BM == 128) vlaunch<E, 128, true, BN, __VA_ARGS__>(a, G, st);                                  \
-      else hipLaunchKernelGGL((vconv_kernel<E, 64, true>), dim3(G), dim3(NT), 0, st, a);                \
+      if (BM == 128) vlaunch<(E) | W, 128, true, BN, __VA_ARGS__>(a, G, st);                                  \
+      else hipLaunchKernelGGL((vconv_kernel<(E) | W, 64, true>), dim3(G), dim3(NT), 0, st, a);                \
     }                                                                                                   \
     break;
+  auto dispatch = [&](auto wtb) -> int {
+  constexpr int W = decltype(wtb)::value;  // VE_WT under the write-through store policy (mt_common.h), else 0
   if (!k1) {
     switch (ef) {
       MT_VCASE(VE_ACT)
@@ -1518,28 +1593,28 @@ int launch_vconv(int ef, const VConvArgs& a0, hipStream_t st) {
       MT_VCASE_HCT(VE_GNSTATS)
       MT_VCASE_HCT(VE_MASK)
       case VE_DUAL:  // the upsamplers (placed polyphase output)
-        if (BM == 128) vlaunch<VE_DUAL, 128, false, BN, 8, 2, 4, 2, 2, 2>(a, G, st);
-        else hipLaunchKernelGGL((vconv_kernel<VE_DUAL, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
+        if (BM == 128) vlaunch<VE_DUAL | W, 128, false, BN, 8, 2, 4, 2, 2, 2>(a, G, st);
+        else hipLaunchKernelGGL((vconv_kernel<VE_DUAL | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
         break;
       MT_VCASE(VE_RELU | VE_MASK)
       case VE_PMASK:  // the decoder's ConvTranspose up conv
-        if (BM == 128) vlaunch<VE_PMASK, 128, false, BN, 4, 2>(a, G, st);
-        else hipLaunchKernelGGL((vconv_kernel<VE_PMASK, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
+        if (BM == 128) vlaunch<VE_PMASK | W, 128, false, BN, 4, 2>(a, G, st);
+        else hipLaunchKernelGGL((vconv_kernel<VE_PMASK | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
         break;
       case VE_RESID | VE_MASK:
-        if (bm64_128) hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK, 64, false, 128>), dim3(G), dim3(NT), 0, st, a);
-        else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK, 128, false>), dim3(G), dim3(NT), 0, st, a);
-        else hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
+        if (bm64_128) hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK | W, 64, false, 128>), dim3(G), dim3(NT), 0, st, a);
+        else if (BM == 128) hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK | W, 128, false>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vconv_kernel<VE_RESID | VE_MASK | W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
         break;
       MT_VCASE(VE_RESID | VE_DIV | VE_DUAL)
       MT_VCASE(VE_RESID | VE_ACCUM | VE_DIV | VE_DUAL)
       case 0:  // plain: the upsamplers whose stage activates its input itself (VE_ACTIN), compile-time K loops
 #if defined(VCONV_UP_NOCT)  // A/B build: the runtime-cursor loop
-        if (BM == 128) hipLaunchKernelGGL((vconv_kernel<0, 128, false>), dim3(G), dim3(NT), 0, st, a);
+        if (BM == 128) hipLaunchKernelGGL((vconv_kernel<W, 128, false>), dim3(G), dim3(NT), 0, st, a);
 #else
-        if (BM == 128) vlaunch<0, 128, false, BN, 8, 2, 4, 2, 2, 2>(a, G, st);
+        if (BM == 128) vlaunch<W, 128, false, BN, 8, 2, 4, 2, 2, 2>(a, G, st);
 #endif
-        else hipLaunchKernelGGL((vconv_kernel<0, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vconv_kernel<W, 64, false, BN64>), dim3(G), dim3(NT), 0, st, a);
         break;
       default: set_error("vconv: epilogue %d not compiled in", ef); return -1;
     }
@@ -1557,11 +1632,17 @@ int launch_vconv(int ef, const VConvArgs& a0, hipStream_t st) {
       default: set_error("vconv: 1x1 epilogue %d not compiled in", ef); return -1;
     }
   }
+  return 0;
+  };
 #undef MT_VCASE
 #undef MT_VCASE_H
 #undef MT_VCASE_HCT
 #undef MT_VCASE1
 #undef MT_VCASE1CT
+  // the buffer stores address the whole output with 32-bit byte offsets below 2^31; a larger one stores plain
+  const bool wt = store_policy() == ST_WT && (long long)a.B * a.ystride * 2 < (1ll << 31);
+  const int drc = wt ? dispatch(std::integral_constant<int, VE_WT>{}) : dispatch(std::integral_constant<int, 0>{});
+  if (drc) return drc;
   MT_CHECK_HIP(hipGetLastError());
   if (probed) probe_end(site, st, flops, bytes);
   return 0;

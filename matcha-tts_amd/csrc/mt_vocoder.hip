@@ -570,6 +570,7 @@ int Vocoder::forward_t(const char* P, const float* mel, int B, int T, float* wav
   int L = T;
   const int nk = (int)rb_kernels.size();
   for (size_t i = 0; i < ups.size(); ++i) {
+    StorePolicyScope pol((wt_stages >> i) & 1 ? ST_WT : ST_PLAIN);  // stage i's launches (wt_stages, mt_model.h)
     ConvArgs u = gemm_args(ups[i], P, B, L);
     u.x0 = XS;
     u.y = X;

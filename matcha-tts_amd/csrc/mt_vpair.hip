@@ -105,8 +105,9 @@ __device__ __forceinline__ void vp_step_barrier() {
 }
 
 
-template <int EF, int K = 0>
+template <int EF, int K = 0, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
+  static_assert(SP == ST_PLAIN || VP_BUF, "the store policy rides on the buffer stores");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -539,11 +540,11 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
           const bool keep = !(fn == FN - 1 && wave == 7);
           const unsigned vo = keep ? (unsigned)(((n0 + i) * C + fp * 32 + ch16) * 2) : 0x80000000u;
           if constexpr ((EF & VE_Y2ONLY) == 0)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo, 0, 0);
+            buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
           if constexpr ((EF & VE_DUAL) != 0) {
             swap16(o2[0][0], o2[1][0]);
             swap16(o2[0][1], o2[1][1]);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo, 0, 0);
+            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
           }
           continue;
         }
@@ -586,7 +587,7 @@ struct K3G {
 };
 }  // namespace
 
-template <int EF, int FNT, bool DB>
+template <int EF, int FNT, bool DB, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
   using G3 = K3G<FNT, DB>;
   __shared__ __attribute__((aligned(1024))) char smem[G3::LDS];
@@ -867,6 +868,19 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
         swap16(o1[0][0], o1[1][0]);
         swap16(o1[0][1], o1[1][1]);
         const bool ok = i < BN && n0 + i < L;
+        if constexpr (SP != ST_PLAIN) {
+          // the same stores through the utterance's [L][C] output as a buffer (the ring kernel's form): a store that is
+          // not ok gets an offset past any range and is dropped; every lane still stores
+          const size_t ub = (size_t)__builtin_amdgcn_readfirstlane(b) * L * C;
+          const unsigned vo = ok ? (unsigned)(((n0 + i) * C + fp * 32 + ch16) * 2) : 0x80000000u;
+          buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, buf_rsrc(a.y + ub, (unsigned)L * (C * 2)), vo);
+          if constexpr ((EF & VE_DUAL) != 0) {
+            swap16(o2[0][0], o2[1][0]);
+            swap16(o2[0][1], o2[1][1]);
+            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, buf_rsrc(a.y2 + ub, (unsigned)L * (C * 2)), vo);
+          }
+          continue;
+        }
         const size_t o = ((size_t)b * L + n0 + i) * C + fp * 32 + ch16;
         *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
         if constexpr ((EF & VE_DUAL) != 0) {
@@ -936,11 +950,14 @@ int launch_vpair(int ef, const VPairArgs& a, hipStream_t st) {
   // probe: the pair is two of the family's convs (SURVEY §8d algorithmic FLOPs and layer-boundary bytes)
   const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
   const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
+  // the store policy (mt_common.h) on the default kernels: the k = 3 "2d" geometry and the compile-time K ring
+  const bool wt = store_policy() == ST_WT;
   probe_begin(PROBE_VCONV, st);
   if (k3) {
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(G), dim3(NT), 0, st, a); };
 #define MT_VP3(E)                                                       \
   (k3mode == 3 ? go(vpair3_kernel<E, 3, false>) : k3mode == 2 ? go(vpair3_kernel<E, 2, false>) \
+   : wt        ? go(vpair3_kernel<E, 2, true, ST_WT>)                                           \
                : go(vpair3_kernel<E, 2, true>))
     switch (ef) {
       case 0: MT_VP3(0); break;
@@ -960,10 +977,12 @@ int launch_vpair(int ef, const VPairArgs& a, hipStream_t st) {
       if (!ctk) hipLaunchKernelGGL((vpair_kernel<E>), dim3(G), dim3(NT), 0, st, a);
       else if (a.taps == 7) {
         (void)VpkReg<2, VpSched<E, 7>, E>::reg;
-        hipLaunchKernelGGL((vpair_kernel<E, 7>), dim3(G), dim3(NT), 0, st, a);
+        if (wt) hipLaunchKernelGGL((vpair_kernel<E, 7, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vpair_kernel<E, 7>), dim3(G), dim3(NT), 0, st, a);
       } else if (a.taps == 11) {
         (void)VpkReg<2, VpSched<E, 11>, E>::reg;
-        hipLaunchKernelGGL((vpair_kernel<E, 11>), dim3(G), dim3(NT), 0, st, a);
+        if (wt) hipLaunchKernelGGL((vpair_kernel<E, 11, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vpair_kernel<E, 11>), dim3(G), dim3(NT), 0, st, a);
       }
       else hipLaunchKernelGGL((vpair_kernel<E>), dim3(G), dim3(NT), 0, st, a);
     };

@@ -109,8 +109,9 @@ __device__ __forceinline__ void step_barrier() {
 
 // K > 0: the compile-time K loop (k = K): steps unrolled, ring slots and vmcnt counts constants (VpkSched), step
 // barriers without an lgkmcnt drain except each conv's first, phantom prefetches past the workgroup's last tile
-template <int EF, int K = 0>
+template <int EF, int K = 0, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
+  static_assert(SP == ST_PLAIN || VP128_BUF, "the store policy rides on the buffer stores");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -511,11 +512,11 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
           // the utterance's [L][C] output as a buffer: frames past L fall outside it (store dropped), the tile's
           // discarded frames i >= BN get an offset past any range; every lane still stores
           const unsigned vo = i < BN ? (unsigned)(((n0 + i) * C + wm * 64 + fp * 32 + ch16) * 2) : 0x80000000u;
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo, 0, 0);
+          buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
           if constexpr ((EF & VE_DUAL) != 0) {
             swap16(o2[0][0], o2[1][0]);
             swap16(o2[0][1], o2[1][1]);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo, 0, 0);
+            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
           }
           continue;
         }
@@ -569,12 +570,15 @@ int launch_vpair128(int ef, const VPairArgs& a, hipStream_t st) {
   probe_begin(PROBE_VCONV, st);
   // the compile-time K loop for k = 3 (mt_vpair_set_kernels bit VPK_CTK128) when its fixed row staging covers R1
   const bool ct3 = a.taps == 3 && (vpair_kernels() & VPK_CTK128) != 0 && NF1 + 2 * a.dil <= 32 * XPW;
+  const bool wt = store_policy() == ST_WT;  // the store policy (mt_common.h)
   auto go = [&](auto ec) {
     constexpr int E = decltype(ec)::value;
     if (ct3) {
       (void)VpkReg<3, Vp128Sched<E, 3>, E>::reg;
-      hipLaunchKernelGGL((vpair128_kernel<E, 3>), dim3(G), dim3(NT), 0, st, a);
+      if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 3, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((vpair128_kernel<E, 3>), dim3(G), dim3(NT), 0, st, a);
     }
+    else if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 0, ST_WT>), dim3(G), dim3(NT), 0, st, a);
     else hipLaunchKernelGGL((vpair128_kernel<E>), dim3(G), dim3(NT), 0, st, a);
   };
   switch (ef) {

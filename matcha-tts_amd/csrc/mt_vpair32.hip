@@ -86,8 +86,9 @@ __device__ __forceinline__ void barrier() {
 }
 }  // namespace
 
-template <int EF>
+template <int EF, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h); the VE_POST waveform stays plain
 __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
+  static_assert(SP == ST_PLAIN || (VP32_BUF && !(EF & VE_POST)), "the store policy rides on the 16-byte buffer stores");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -376,11 +377,11 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
         // the issue counts are unchanged)
         const bool keep = !(fn == FN - 1 && wave == 7);
         const unsigned vo = keep ? (unsigned)(((n0 + i) * C + ch16) * 2) : 0x80000000u;
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo, 0, 0);
+        buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
         if constexpr ((EF & VE_DUAL) != 0) {
           swap16(o2[0][0], o2[1][0]);
           swap16(o2[0][1], o2[1][1]);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo, 0, 0);
+          buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
         }
         continue;
       }
@@ -469,16 +470,20 @@ int launch_vpair32(int ef, const VPairArgs& a, hipStream_t st) {
   const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
   const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
   probe_begin(PROBE_VCONV, st);
+  const bool wt = store_policy() == ST_WT;  // the store policy (mt_common.h)
+#define MT_VP32(E)                                                                                 \
+  if (wt) hipLaunchKernelGGL((vpair32_kernel<(E), ST_WT>), dim3(G), dim3(NT), 0, st, a);           \
+  else hipLaunchKernelGGL((vpair32_kernel<(E)>), dim3(G), dim3(NT), 0, st, a);                     \
+  break
   switch (ef) {
-    case 0: hipLaunchKernelGGL((vpair32_kernel<0>), dim3(G), dim3(NT), 0, st, a); break;
-    case VE_ACCUM: hipLaunchKernelGGL((vpair32_kernel<VE_ACCUM>), dim3(G), dim3(NT), 0, st, a); break;
-    case VE_ACCUM | VE_DIV: hipLaunchKernelGGL((vpair32_kernel<VE_ACCUM | VE_DIV>), dim3(G), dim3(NT), 0, st, a); break;
-    case VE_ACCUM | VE_DIV | VE_DUAL:
-      hipLaunchKernelGGL((vpair32_kernel<VE_ACCUM | VE_DIV | VE_DUAL>), dim3(G), dim3(NT), 0, st, a);
-      break;
-    case VE_DIV: hipLaunchKernelGGL((vpair32_kernel<VE_DIV>), dim3(G), dim3(NT), 0, st, a); break;
-    case VE_DIV | VE_DUAL: hipLaunchKernelGGL((vpair32_kernel<VE_DIV | VE_DUAL>), dim3(G), dim3(NT), 0, st, a); break;
-    case VE_ACCUM | VE_DIV | VE_POST:
+    case 0: MT_VP32(0);
+    case VE_ACCUM: MT_VP32(VE_ACCUM);
+    case VE_ACCUM | VE_DIV: MT_VP32(VE_ACCUM | VE_DIV);
+    case VE_ACCUM | VE_DIV | VE_DUAL: MT_VP32(VE_ACCUM | VE_DIV | VE_DUAL);
+    case VE_DIV: MT_VP32(VE_DIV);
+    case VE_DIV | VE_DUAL: MT_VP32(VE_DIV | VE_DUAL);
+#undef MT_VP32
+    case VE_ACCUM | VE_DIV | VE_POST:  // 4-byte waveform stores only: plain under every policy
       hipLaunchKernelGGL((vpair32_kernel<VE_ACCUM | VE_DIV | VE_POST>), dim3(G), dim3(NT), 0, st, a);
       break;
     default: set_error("vpair32: epilogue %d not compiled in", ef); return -1;

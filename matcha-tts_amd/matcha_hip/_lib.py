@@ -39,6 +39,7 @@ SIGNATURES = {
     "mt_encoder_set_mfma_attention": (c_int, [P, c_int]),
     "mt_encoder_set_vconv": (c_int, [P, c_int]),
     "mt_encoder_set_split": (c_int, [P, c_int]),
+    "mt_encoder_set_store_policy": (c_int, [P, c_int]),
     "mt_encoder_forward": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "mt_decoder_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "mt_decoder_destroy": (None, [P]),
@@ -68,6 +69,7 @@ SIGNATURES = {
     "mt_vocoder_set_fusion": (c_int, [P, c_int]),
     "mt_vocoder_set_vconv": (c_int, [P, c_int]),
     "mt_vocoder_set_pair": (c_int, [P, c_int]),
+    "mt_vocoder_set_store_policy": (c_int, [P, c_int]),
     "mt_decoder_set_vconv": (c_int, [P, c_int]),
     "mt_vocoder_pack": (c_int, [P, POINTER(c_void_p), P, P]),
     "mt_vocoder_workspace_bytes": (c_size_t, [P, c_int, c_int]),

@@ -186,6 +186,11 @@ class EncoderEngine:
         """fp32: the FFN convs on mt_vconv's split-bf16 mode (1; precision "fp32x3") or exact fp32 MFMA (0)."""
         check(lib().mt_encoder_set_split(self.h, int(bool(enable))), "encoder_set_split")
 
+    def set_store_policy(self, mode) -> None:
+        """the mt_vconv launches' 16-byte output stores: 0 plain (default), 1 write-through (sc1); same bits. Any
+        other mode raises."""
+        check(lib().mt_encoder_set_store_policy(self.h, int(mode)), "encoder_set_store_policy")
+
     def pack(self, params: Dict[str, torch.Tensor], device: torch.device) -> torch.Tensor:
         """params: TextEncoder-relative reference keys -> tensors."""
         tensors = []
@@ -396,6 +401,11 @@ class VocoderEngine:
         """bf16 ResBlock pairs as one launch each: 1 (default) the 64- / 32-channel stages and the 128-channel
         stage's k = 3 resblock; 4 every 128-channel pair too; 2 none of the 128-channel stage; 0 all per layer."""
         check(lib().mt_vocoder_set_pair(self.h, int(mode)), "vocoder_set_pair")
+
+    def set_store_policy(self, stage_mask) -> None:
+        """bit i: stage i's launches store their 16-byte outputs write-through (sc1) instead of plain (0, the
+        default, everywhere); same bits. A mask naming a missing stage raises."""
+        check(lib().mt_vocoder_set_store_policy(self.h, int(stage_mask)), "vocoder_set_store_policy")
 
     def set_vconv(self, mode) -> None:
         """0 generic per-layer kernel, 1 vconv for the 128/256-channel stages, 2 (default) also for 64."""
@@ -715,8 +725,9 @@ def set_ffn_min_frames(frames: int) -> int:
 
 def set_decoder_kernels(mask: int) -> int:
     """the decoder kernel variants (bit 0: the dedicated final projection + ODE update kernel; bit 1: the
-    query-independent attention's o_b computed once per solve instead of once per evaluation; default 3), each
-    bit-identical to what it replaces; returns the previous mask (process-wide)"""
+    query-independent attention's o_b computed once per solve instead of once per evaluation; bits 2 / 3, values
+    4 / 8: write-through output stores at level 0 / level 1; default 15), each bit-identical to what it replaces;
+    returns the previous mask (process-wide)"""
     return int(lib().mt_decoder_set_kernels(int(mask)))
 
 

@@ -2,7 +2,8 @@
 """In-process A/B of the decoder kernel variants (mt_decoder_set_kernels masks, bit-identical): the bf16 CFM solve
 (10-step Euler, graph path) at B x T, ragged like the bench (the longest utterance T - 4 frames, so the
 query-independent attention runs at both levels), interleaved rounds, median and min per mask; checks the outputs
-are equal. Default: mask 1 (o_b recomputed in every evaluation) against mask 3 (o_b once per solve).
+are equal. Default: mask 1 (o_b recomputed in every evaluation) against mask 3 (o_b once per solve). The store
+policy's bits: masks 3,7,11,15 (plain, level 0, level 1, both write-through).
 Usage: python tools/deck_ab.py [B] [T] [rounds] [masks, e.g. 0,1]"""
 import os
 import sys
