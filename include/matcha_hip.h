@@ -152,6 +152,25 @@ int mt_cfm_solve_bounded(const mt_decoder* d, const void* packed, const float* z
 int mt_cfm_solve_seeded(const mt_decoder* d, const void* packed, const int64_t* seeds, const float* temperature,
                         const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
                         int n_timesteps, int solver, float* z_out, void* ws, size_t ws_bytes, void* stream);
+/* One solve with a step count and a time grid per utterance. The rows come sorted by step count: n_steps (int32 [B],
+ * host, each >= 1) is non-increasing, anything else is an error; callers sort their own rows. Utterance b takes the
+ * Euler / midpoint steps i = 0 .. n_steps[b] - 1 at time t[b][i] with step dt[b][i] (fp32 [B][n_steps[0]] row-major,
+ * host; entries past a row's count are not read; t in [0, 1], dt in (0, 1]), or, with t and dt both NULL, the
+ * reference's grid t = (float)(i / n_b), dt = (float)(1 / n_b) (model.py:1086-1104), on which a row's arithmetic is
+ * that of mt_cfm_solve_bounded with n_timesteps = n_b. After its last step no launch includes the row: evaluation i
+ * runs on the first rows_per_eval[i] rows (mt_cfm_rows_plan): the solve costs sum_i rows_per_eval[i] row-evaluations.
+ * Exactly one of z_noise ([B,80,T]) and seeds (int64 [B], device; mt_cfm_solve_seeded's stream) is given;
+ * temperature: fp32 [B], device, NULL = 1. The host arrays are consumed before the call returns. Launched directly on
+ * the stream (no hipGraph, nothing cached). Workspace: mt_cfm_rows_workspace_bytes(d, B, T, n_steps[0], solver). */
+size_t mt_cfm_rows_workspace_bytes(const mt_decoder* d, int B, int T, int n_max, int solver);
+/* Host only (no GPU call): the number of estimator evaluations S of such a solve (n_steps[0] for Euler, twice that
+ * for midpoint), with rows_per_eval[i] = the rows evaluation i runs on; negative (mt_last_error) for an empty batch,
+ * a count < 1, an increasing pair or cap < S. */
+int mt_cfm_rows_plan(const int32_t* n_steps, int B, int solver, int32_t* rows_per_eval, int cap);
+int mt_cfm_solve_rows(const mt_decoder* d, const void* packed, const float* z_noise, const int64_t* seeds,
+                      const float* temperature, const float* mu_y, const float* mask, const float* spks, int B, int T,
+                      int max_valid, const int32_t* n_steps, const float* t, const float* dt, int solver, float* z_out,
+                      void* ws, size_t ws_bytes, void* stream);
 /* Seeded Gaussian noise, z [B,C,T] fp32 (C % 4 == 0): z[b,c,t] depends on (seeds[b], c, t) only, not on B, T or the
  * row's position. Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) of the int64 seed's two's-complement uint64
  * on the counter (t, c / 4, 0, 0); each output word x gives u(x) = (2 (x >> 9) + 1) 2^-24; channels 4q, 4q + 1 are

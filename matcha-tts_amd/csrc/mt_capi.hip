@@ -192,6 +192,31 @@ int mt_cfm_solve_seeded(const mt_decoder* d, const void* packed, const int64_t* 
   return d->d.solve(packed, nullptr, 1.f, mu_y, mask, spks, B, T, n_timesteps, solver, z_out, ws, ws_bytes,
                     (hipStream_t)stream, max_valid, (const long long*)seeds, temperature);
 }
+size_t mt_cfm_rows_workspace_bytes(const mt_decoder* d, int B, int T, int n_max, int solver) {
+  if (!d || B <= 0 || T <= 0 || n_max <= 0) return 0;
+  return d->d.rows_workspace_bytes(B, T, solver == 1 ? 2 * n_max : n_max);
+}
+int mt_cfm_rows_plan(const int32_t* n_steps, int B, int solver, int32_t* rows_per_eval, int cap) {
+  return mt::rows_plan(n_steps, B, solver, rows_per_eval, cap);
+}
+int mt_cfm_solve_rows(const mt_decoder* d, const void* packed, const float* z_noise, const int64_t* seeds,
+                      const float* temperature, const float* mu_y, const float* mask, const float* spks, int B, int T,
+                      int max_valid, const int32_t* n_steps, const float* t, const float* dt, int solver, float* z_out,
+                      void* ws, size_t ws_bytes, void* stream) {
+  MT_REQUIRE(d, "cfm_solve_rows: decoder is NULL");
+  MT_REQUIRE(packed, "cfm_solve_rows: packed is NULL");
+  MT_REQUIRE(z_noise || seeds, "cfm_solve_rows: z_noise and seeds are both NULL (give one)");
+  MT_REQUIRE(!(z_noise && seeds), "cfm_solve_rows: z_noise and seeds are both given (give one)");
+  MT_REQUIRE(mu_y, "cfm_solve_rows: mu_y is NULL");
+  MT_REQUIRE(mask, "cfm_solve_rows: mask is NULL");
+  MT_REQUIRE(n_steps, "cfm_solve_rows: n_steps is NULL");
+  MT_REQUIRE((t == nullptr) == (dt == nullptr), "cfm_solve_rows: t and dt come together (%s is NULL)",
+             t ? "dt" : "t");
+  MT_REQUIRE(z_out, "cfm_solve_rows: z_out is NULL");
+  MT_REQUIRE(ws, "cfm_solve_rows: workspace is NULL");
+  return d->d.solve_rows(packed, z_noise, (const long long*)seeds, temperature, mu_y, mask, spks, B, T, max_valid,
+                         n_steps, t, dt, solver, z_out, ws, ws_bytes, (hipStream_t)stream);
+}
 int mt_noise_fill(const int64_t* seeds, const float* temperature, int B, int C, int T, float* z, void* stream) {
   MT_REQUIRE(seeds, "noise_fill: seeds is NULL");
   MT_REQUIRE(z, "noise_fill: z is NULL");

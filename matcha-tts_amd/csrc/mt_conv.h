@@ -78,7 +78,8 @@ struct ConvArgs {
   void* xin_z;               // estimator input slot (element type), row stride ld_xin
   int ld_xin;
   float dt;
-  int half_step;             // midpoint first half: inc = (pred*dt)*0.5
+  const float* dt_rows;      // [B] or null: utterance b steps by dt_rows[b] instead of dt (Decoder::solve_rows)
+  int half_step;            // midpoint first half: inc = (pred*dt)*0.5
   int update_master;
   // ragged batch (the fp32 vocoder's per-utterance lengths, mt_ragged.h): utterance b's input has lens[b] * lmul
   // valid frames (zero padding past them); tiles past its output columns exit, outputs past them are not written

@@ -391,10 +391,11 @@ __global__ __launch_bounds__(TL::NT) void conv_kernel(ConvArgs a) {
       if constexpr ((EF & EF_EULER) != 0) {
         E* xz = reinterpret_cast<E*>(a.xin_z) + orow * a.ld_xin + ch;
         float* zp = a.zmaster + orow * a.cout + ch;
+        const float dt = a.dt_rows ? a.dt_rows[b] : a.dt;  // orow's utterance, uniform over the tile
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if (!ok[r]) continue;
-          float inc = v[r] * a.dt;
+          float inc = v[r] * dt;
           if (a.half_step) inc = inc * 0.5f;
           const float zn = zp[r] + inc;
           if (a.update_master) zp[r] = zn;
@@ -590,6 +591,7 @@ __global__ __launch_bounds__(256) void proj_euler_kernel(ConvArgs a) {
   if (!fok) return;
   // epilogue (conv_kernel's EF_MASK | EF_EULER): rows 16 mb + 4 (lane >> 4) + r of frame f
   const size_t orow = (size_t)b * a.Tout + f;
+  const float dt = a.dt_rows ? a.dt_rows[b] : a.dt;  // b is the workgroup's utterance: one uniform load
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     const int ch = 16 * mb + 4 * kq;
@@ -605,7 +607,7 @@ __global__ __launch_bounds__(256) void proj_euler_kernel(ConvArgs a) {
     bf16x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float inc = v[r] * a.dt;
+      float inc = v[r] * dt;
       if (a.half_step) inc = inc * 0.5f;
       const float zn = z4[r] + inc;
       zn4[r] = zn;

@@ -10,9 +10,11 @@
 //                    estimator input slot for the next evaluation.
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
+#include <unordered_map>
 
 #include "mt_ffn.h"
 #include "mt_model.h"
@@ -743,8 +745,12 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
   const bool mio = vconv && std::is_same<E, bf16>::value;
   bool rs = false;  // the last resnet's output conv wrote the LayerNorm partials of its output
   // DECK_OVEC: transformer block j of resnet r keeps its o_b in slot (blocks before resnet r) + j of w.uvec;
-  // evaluation 0 of the chain (and a single evaluation: step, step_times) computes it, the later ones read it
+  // evaluation 0 of the chain (and a single evaluation: step, step_times) computes it, the later ones read it.
+  // solve_rows: evaluation 0 runs on the whole batch and fills every row's [256] piece of each slot; its later
+  // evaluations run on a prefix of the rows and index the same slots (stride w.uvec_B rows) by row, so `ev > 0`
+  // below still means "this row's o_b is there"
   const bool ovk = std::is_same<E, bf16>::value && (dec_kernels() & DECK_OVEC);
+  const size_t uvB = w.uvec_B ? w.uvec_B : B;
   // DECK_WT0 / DECK_WT1: the store policy of this evaluation's launches, by the level whose frames they write (the
   // down conv writes level 1, the up conv level 0)
   const bool l0fits = (size_t)B * T * C * sizeof(bf16) <= kDeckWt0MaxBytes;
@@ -756,7 +762,7 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
     size_t slot = 0;
     for (int i = 0; i < r; ++i) slot += tbs[i].size();
     for (int j = 0; j < nb; ++j) {
-      float* us = ovk ? w.uvec + (slot + j) * (size_t)B * C : nullptr;
+      float* us = ovk ? w.uvec + (slot + j) * uvB * C : nullptr;
       int e = tblock<E>(P, w, tbs[r][j], x, m, mio && j == nb - 1, rs && j == 0, uni, us, ovk && ev > 0, B, Tl, st);
       if (e) return e;
     }
@@ -875,6 +881,7 @@ int Decoder::eval(const char* P, const Work& w, int B, int T, int ev, const Eule
   f.xin_z = w.xin;
   f.ld_xin = xld();
   f.dt = eu.dt;
+  f.dt_rows = eu.dt_rows;
   f.half_step = eu.half_step;
   f.update_master = eu.update_master;
   if (std::is_same<E, bf16>::value && (dec_kernels() & DECK_PROJ) && proj_euler_supported(f))
@@ -892,8 +899,9 @@ int Decoder::init_inputs(const Work& w, const float* z, float temperature, const
     // the fp32 master and the z slot of xin straight from the generator: no [B,80,T] noise tensor to transpose
     if ((rc = noise_fill_decoder(dtype, seeds, temp_dev, B, T, w.zm, w.xin, ld, st))) return rc;
   } else {
-    if ((rc = bct_to_btc(F32, z, B, NF, T, temperature, w.zm, NF, 0, st))) return rc;
-    if ((rc = bct_to_btc(dtype, z, B, NF, T, temperature, w.xin, ld, 0, st))) return rc;
+    // temp_dev with z (solve_rows): one temperature per utterance in place of the shared one
+    if ((rc = bct_to_btc(F32, z, B, NF, T, temperature, w.zm, NF, 0, st, temp_dev))) return rc;
+    if ((rc = bct_to_btc(dtype, z, B, NF, T, temperature, w.xin, ld, 0, st, temp_dev))) return rc;
   }
   if ((rc = bct_to_btc(dtype, mu_y, B, NF, T, 1.f, w.xin, ld, NF, st))) return rc;
   if (c_cond > 2 * NF) {
@@ -1091,6 +1099,149 @@ int Decoder::step_times(const void* packed, const float* x, const float* mu_y, c
   rc = dtype == BF16 ? eval<bf16>(P, w, B, T, 0, eu, st) : eval<float>(P, w, B, T, 0, eu, st);
   if (rc) return rc;
   return btc_to_bct(F32, w.zm, NF, 0, B, NF, T, out, st);
+}
+
+// ---- one solve, a step count and a time grid per utterance (mt_cfm_solve_rows) ----
+int rows_plan(const int* n_steps, int B, int solver, int* rows_per_eval, int cap) {
+  MT_REQUIRE(n_steps && rows_per_eval, "cfm_rows_plan: null argument");
+  MT_REQUIRE(B > 0, "cfm_rows_plan: empty batch (B = %d)", B);
+  MT_REQUIRE(solver == 0 || solver == 1, "cfm_rows_plan: solver must be 0 (euler) or 1 (midpoint)");
+  for (int b = 0; b < B; ++b) {
+    MT_REQUIRE(n_steps[b] >= 1, "cfm_rows_plan: n_steps[%d] = %d must be >= 1", b, n_steps[b]);
+    MT_REQUIRE(b == 0 || n_steps[b] <= n_steps[b - 1],
+               "cfm_rows_plan: n_steps[%d] = %d > n_steps[%d] = %d (rows must be sorted by step count, descending)", b,
+               n_steps[b], b - 1, n_steps[b - 1]);
+  }
+  const int per = solver == 0 ? 1 : 2;
+  MT_REQUIRE(n_steps[0] <= (cap < 0 ? 0 : cap) / per, "cfm_rows_plan: %d steps x %d evaluations each > cap %d",
+             n_steps[0], per, cap);
+  int rows = B;
+  for (int i = 0; i < n_steps[0]; ++i) {
+    while (n_steps[rows - 1] <= i) --rows;  // rows whose last step was i - 1 retire; row 0 has n_steps[0] > i
+    for (int k = 0; k < per; ++k) rows_per_eval[per * i + k] = rows;
+  }
+  return per * n_steps[0];
+}
+
+namespace {
+// The tables go to the device as kernel arguments, a piece per launch: the launch copies its arguments, so the
+// caller's host arrays are free when solve_rows returns, whatever kind of host memory they live in.
+struct TablePiece {
+  static constexpr int N = 512;
+  unsigned v[N];  // fp32 bit patterns / ints
+};
+__global__ void table_piece_kernel(TablePiece p, unsigned* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = p.v[i];
+}
+// dst row r = src row idx[r] (ld floats, ld % 4 == 0): the time biases of the distinct times laid out per
+// (evaluation, utterance)
+__global__ __launch_bounds__(256) void rows_expand_kernel(const float* __restrict__ src, const int* __restrict__ idx,
+                                                          int ld, float* __restrict__ dst) {
+  const size_t r = blockIdx.x;
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(src + (size_t)idx[r] * ld);
+  f32x4* d4 = reinterpret_cast<f32x4*>(dst + r * ld);
+  for (int c = threadIdx.x; c < ld / 4; c += 256) d4[c] = s4[c];
+}
+}  // namespace
+
+size_t Decoder::rows_workspace_bytes(int B, int T, int S) const {
+  const size_t SB = (size_t)S * B;
+  return workspace_bytes(B, T, S * B) + align256(3 * SB * 4) + align256(SB * n_res * C * 4);
+}
+
+int Decoder::solve_rows(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
+                        const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
+                        const int* n_steps, const float* t, const float* dt, int solver, float* z_out, void* ws,
+                        size_t ws_bytes, hipStream_t st) const {
+  int rc;
+  if ((rc = check_geom(B, T))) return rc;
+  MT_REQUIRE(solver == 0 || solver == 1, "cfm: solver must be 0 (euler) or 1 (midpoint)");
+  MT_REQUIRE(n_steps, "cfm_solve_rows: n_steps is NULL");
+  MT_REQUIRE(n_steps[0] >= 1 && n_steps[0] <= kRowsMaxSteps, "cfm_solve_rows: n_steps[0] = %d outside [1, %d]",
+             n_steps[0], kRowsMaxSteps);
+  const int n_max = n_steps[0], per = solver == 0 ? 1 : 2;
+  std::vector<int> rows((size_t)per * n_max);
+  const int S = rows_plan(n_steps, B, solver, rows.data(), (int)rows.size());
+  if (S < 0) return S;
+  MT_REQUIRE(ws_bytes >= rows_workspace_bytes(B, T, S), "cfm_solve_rows: workspace %zu < %zu", ws_bytes,
+             rows_workspace_bytes(B, T, S));
+  MT_REQUIRE(max_valid >= 0 && max_valid <= T, "cfm: max_valid %d outside [0, T=%d]", max_valid, T);
+  const char* P = (const char*)packed;
+  Work w = carve(ws, B, T, S * B);
+  w.m0 = mask;
+  w.uni0 = max_valid > 0 && max_valid < T;  // a bound on every row: it holds for any prefix of them
+  w.uni1 = max_valid > 0 && max_valid <= T - 2;
+  w.tb_ld = n_res * C;
+  w.uvec_B = B;
+  // Host tables: the U distinct evaluation times (the time MLPs run once per distinct time; a batch with a few step
+  // counts has a few dozen, a grid per utterance up to S * B), the [S][B] steps, and the [S][B] index of each
+  // (evaluation, utterance)'s time among the distinct ones. A row's entries past its last evaluation are read by no
+  // evaluation (step 0, index 0).
+  const size_t SB = (size_t)S * B;
+  std::vector<unsigned> ut, hd(SB, 0u), hi(SB, 0u);
+  std::unordered_map<unsigned, int> seen;
+  auto bits = [](float v) {
+    unsigned u;
+    memcpy(&u, &v, sizeof u);
+    return u;
+  };
+  auto put = [&](int ev, int b, float tv, float dv) {
+    auto it = seen.find(bits(tv));
+    if (it == seen.end()) {
+      it = seen.emplace(bits(tv), (int)ut.size()).first;
+      ut.push_back(bits(tv));
+    }
+    hd[(size_t)ev * B + b] = bits(dv);
+    hi[(size_t)ev * B + b] = (unsigned)it->second;
+  };
+  for (int b = 0; b < B; ++b) {
+    const float dt_ref = (float)(1.0 / (double)n_steps[b]);
+    for (int i = 0; i < n_steps[b]; ++i) {
+      // the reference's fp32 grid (model.py:1086-1104) unless the caller brings one
+      const float ti = t ? t[(size_t)b * n_max + i] : (float)((double)i / (double)n_steps[b]);
+      const float di = dt ? dt[(size_t)b * n_max + i] : dt_ref;
+      MT_REQUIRE(ti >= 0.f && ti <= 1.f && di > 0.f && di <= 1.f, "cfm_solve_rows: row %d step %d: t %g, dt %g", b, i,
+                 (double)ti, (double)di);
+      if (solver == 0) {
+        put(i, b, ti, di);
+      } else {
+        put(2 * i, b, ti, di);
+        put(2 * i + 1, b, ti + di * 0.5f, di);
+      }
+    }
+  }
+  const size_t U = ut.size();  // 1 <= U <= SB
+  std::vector<unsigned> tab(ut);
+  tab.insert(tab.end(), hd.begin(), hd.end());
+  tab.insert(tab.end(), hi.begin(), hi.end());
+  // device: [U] times, [S][B] steps, [S][B] indices (room for U = SB), then the [S][B][n_res * C] time biases
+  unsigned* dev_tab = (unsigned*)((char*)ws + workspace_bytes(B, T, S * B));
+  const float* t_uniq = (const float*)dev_tab;
+  const float* dt_tab = (const float*)(dev_tab + U);
+  const int* idx_tab = (const int*)(dev_tab + U + SB);
+  float* tb_rows = (float*)((char*)dev_tab + align256(3 * SB * 4));
+  for (size_t o = 0; o < tab.size(); o += TablePiece::N) {
+    TablePiece pc;
+    const int n = (int)std::min((size_t)TablePiece::N, tab.size() - o);
+    std::copy(tab.begin() + (long)o, tab.begin() + (long)o + n, pc.v);
+    hipLaunchKernelGGL(table_piece_kernel, dim3((TablePiece::N + 255) / 256), dim3(256), 0, st, pc, dev_tab + o, n);
+    MT_CHECK_HIP(hipGetLastError());
+  }
+  if ((rc = init_inputs(w, z_noise, 1.f, mu_y, spks, B, T, st, seeds, temp_dev))) return rc;
+  // the time embedding and every ResnetBlock's time bias per distinct time into w.tb [U][n_res * C], then laid out
+  // per (evaluation, utterance)
+  if ((rc = time_embed(P, w, TimeSched{}, (int)U, st, t_uniq))) return rc;
+  hipLaunchKernelGGL(rows_expand_kernel, dim3((unsigned)SB), dim3(256), 0, st, w.tb, idx_tab, n_res * C, tb_rows);
+  MT_CHECK_HIP(hipGetLastError());
+  for (int i = 0; i < S; ++i) {
+    Work wi = w;
+    wi.tb = tb_rows + (size_t)i * B * n_res * C;  // evaluation i's block of per-utterance time biases
+    Euler eu{0.f, solver == 1 && i % 2 == 0, solver == 0 || i % 2 == 1, dt_tab + (size_t)i * B};
+    rc = dtype == BF16 ? eval<bf16>(P, wi, rows[i], T, i, eu, st) : eval<float>(P, wi, rows[i], T, i, eu, st);
+    if (rc) return rc;
+  }
+  return btc_to_bct(F32, w.zm, NF, 0, B, NF, T, z_out, st);
 }
 
 }  // namespace mt

@@ -15,8 +15,9 @@ int rowstats(int dtype, const void* x, int rows, int C, float eps, float* stats,
 int fold_bias(const float* W, const float* beta, int M, int K, float* out, hipStream_t st);
 int pack_vec(const float* src, int period, int n, int op, float* out, hipStream_t st);
 
+// scale_rows (optional, [B] in device memory): utterance b is scaled by scale_rows[b] instead of scale
 int bct_to_btc(int dtype, const float* src, int B, int C, int T, float scale, void* dst, int ld, int coff,
-               hipStream_t st);
+               hipStream_t st, const float* scale_rows = nullptr);
 int btc_to_bct(int dtype, const void* src, int ld, int coff, int B, int C, int T, float* dst,
                hipStream_t st);
 // Seeded noise (mt_noise.hip): the value at (seeds[b], channel, frame) times temp[b] (temp NULL: 1), a pure function

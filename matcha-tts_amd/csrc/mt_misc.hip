@@ -145,10 +145,11 @@ int rowstats(int dtype, const void* x, int rows, int C, float eps, float* stats,
 // layout transposes  [B][C][T] fp32  <->  [B][T][ld] (column offset coff)
 // ------------------------------------------------------------------------------------
 template <class E>
-__global__ void bct_to_btc_kernel(const float* __restrict__ src, int C, int T, float scale,
-                                  E* __restrict__ dst, int ld, int coff) {
+__global__ void bct_to_btc_kernel(const float* __restrict__ src, int C, int T, float scale0,
+                                  const float* __restrict__ scale_rows, E* __restrict__ dst, int ld, int coff) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, c0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+  const float scale = scale_rows ? scale_rows[b] : scale0;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
   for (int i = ty; i < 32; i += 8) {
     const int c = c0 + i, t = t0 + tx;
@@ -179,14 +180,14 @@ __global__ void btc_to_bct_kernel(const E* __restrict__ src, int ld, int coff, i
 }
 
 int bct_to_btc(int dtype, const float* src, int B, int C, int T, float scale, void* dst, int ld,
-               int coff, hipStream_t st) {
+               int coff, hipStream_t st, const float* scale_rows) {
   dim3 grid((T + 31) / 32, (C + 31) / 32, B);
   if (dtype == BF16)
-    hipLaunchKernelGGL(bct_to_btc_kernel<bf16>, grid, dim3(256), 0, st, src, C, T, scale, (bf16*)dst, ld,
-                       coff);
-  else
-    hipLaunchKernelGGL(bct_to_btc_kernel<float>, grid, dim3(256), 0, st, src, C, T, scale, (float*)dst,
+    hipLaunchKernelGGL(bct_to_btc_kernel<bf16>, grid, dim3(256), 0, st, src, C, T, scale, scale_rows, (bf16*)dst,
                        ld, coff);
+  else
+    hipLaunchKernelGGL(bct_to_btc_kernel<float>, grid, dim3(256), 0, st, src, C, T, scale, scale_rows,
+                       (float*)dst, ld, coff);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -266,10 +267,10 @@ int sinus_embed(const TimeSched& ts, int S, const float* freq, int half, float* 
 
 // y[s][yoff + o] = post( sum_i W[o][i] * pre(x[s][i]) + bias[o] ); one wave per output o.
 // pre: 0 none, 1 mish ; post: 0 none, 1 silu, 2 mish
-// The time-embedding MLPs (model.py TimestepEmbedding, ResnetBlock1D.mlp): S <= 128 rows, I <= 1024.
+// The time-embedding MLPs (model.py TimestepEmbedding, ResnetBlock1D.mlp): S <= 128 rows per workgroup, I <= 1024.
 // pre(x) of RD_S rows is staged once per block in LDS, each wave keeps its output's weight row in
 // registers across all rows; per (s, o) the lane-strided sum + wave reduction order is fixed.
-constexpr int RD_S = 8, RD_NO = 2, RD_IMAX = 1024;
+constexpr int RD_S = 8, RD_NO = 2, RD_IMAX = 1024, RD_ROWS_PER_WG = 128;
 __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ x, int ldx,
                                                      const float* __restrict__ W,
                                                      const float* __restrict__ bias, float* __restrict__ y,
@@ -334,8 +335,11 @@ __global__ __launch_bounds__(256) void rowdot4_kernel(const float* __restrict__ 
     const int i4 = lane + 64 * k;
     wv[k] = (o < O && i4 < I4) ? W4[(size_t)o * I4 + i4] : f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  for (int s0 = 0; s0 < S; s0 += RD_S) {
-    const int ns = min(RD_S, S - s0);
+  // rows [s_lo, s_hi) of this workgroup: all S of them unless the launch splits the rows over gridDim.y
+  const int rows_per = (S + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int s_lo = (int)blockIdx.y * rows_per, s_hi = min(S, s_lo + rows_per);
+  for (int s0 = s_lo; s0 < s_hi; s0 += RD_S) {
+    const int ns = min(RD_S, s_hi - s0);
     __syncthreads();
     for (int e = threadIdx.x; e < ns * I4; e += 256) {
       const int r = e / I4, i4 = e - r * I4;
@@ -371,8 +375,10 @@ int rowdot_segs(const float* x, int ldx, const RowdotSegs& sg, float* y, int ldy
                  sg.n <= ROWDOT_MAXSEG,
              "rowdot_segs: I %d (max %d, multiple of 4), ldx %d, S %d, O %d, %d segments", I, RD_IMAX, ldx, S, O,
              sg.n);
-  hipLaunchKernelGGL(rowdot4_kernel, dim3(sg.n * ((O + 3) / 4)), dim3(256), 0, st, x, ldx, sg, y, ldy, S, O, I, pre,
-                     post);
+  // more than RD_ROWS_PER_WG rows (solve_rows: evaluations x utterances): split them over gridDim.y; a row's sum does
+  // not depend on the split
+  hipLaunchKernelGGL(rowdot4_kernel, dim3(sg.n * ((O + 3) / 4), (S + RD_ROWS_PER_WG - 1) / RD_ROWS_PER_WG), dim3(256),
+                     0, st, x, ldx, sg, y, ldy, S, O, I, pre, post);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -121,7 +121,8 @@ struct Decoder {
     float* uvec;   // ... its o_b per transformer block, [n_tblocks()][B][256] (DECK_OVEC): written by the first
                    // evaluation of a solve_chain, read by the later ones
     float* mst;    // the solve's staged copy of the caller's mask (graph replays read only the workspace)
-    int tb_ld;     // 0: one time bias per evaluation; n_res * C: one per utterance (step_times)
+    int tb_ld;     // 0: one time bias per evaluation; n_res * C: one per utterance (step_times, solve_rows)
+    int uvec_B = 0;  // batch stride of the uvec slots when an evaluation runs on a prefix of the batch (0: its own B)
     const float* m0;
     // every utterance has padded frames at the full- / half-resolution level (the caller's max_valid < T /
     // <= T - 2): the transformer blocks there take the query-independent attention path
@@ -137,6 +138,7 @@ struct Decoder {
   struct Euler {
     float dt;
     int half_step, update_master;
+    const float* dt_rows = nullptr;  // [B] in device memory: one step per utterance instead of dt (solve_rows)
   };
   template <class E>
   int eval(const char* P, const Work& w, int B, int T, int ev, const Euler& eu, hipStream_t st) const;
@@ -170,6 +172,18 @@ struct Decoder {
             const float* mask, const float* spks, int B, int T, int n_steps, int solver, float* z_out,
             void* ws, size_t ws_bytes, hipStream_t st, int max_valid = 0, const long long* seeds = nullptr,
             const float* temp_dev = nullptr) const;
+  // One solve with a step count and a time grid per utterance (mt_cfm_solve_rows). Rows sorted by n_steps
+  // (host, [B], non-increasing); t / dt (host, [B][n_steps[0]] row-major, or both null: the reference grid i / n_b
+  // with dt = 1 / n_b). Evaluation i runs on the first rows_plan()[i] rows only, launched directly on st (no graph);
+  // a row's master is what its last update stored. The host arrays are consumed before the call returns.
+  int solve_rows(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
+                 const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
+                 const int* n_steps, const float* t, const float* dt, int solver, float* z_out, void* ws,
+                 size_t ws_bytes, hipStream_t st) const;
+  // workspace of solve_rows: the shared-time workspace with room for S * B distinct times, the [S][B] step / index tables
+  // and the [S][B][n_res * C] per-utterance time biases
+  size_t rows_workspace_bytes(int B, int T, int S) const;
+  static constexpr int kRowsMaxSteps = 1024;  // per utterance (solve_rows)
   // 1 (default): the query-independent attention path when the caller's max_valid allows it; 0: always the
   // general Q.K^T path (A/B, tests)
   int uniform_attn = 1;
@@ -193,6 +207,11 @@ struct Decoder {
   int step_times(const void* packed, const float* x, const float* mu_y, const float* mask, const float* spks,
                  const float* t_dev, int B, int T, float* out, void* ws, size_t ws_bytes, hipStream_t st) const;
 };
+
+// The evaluations of a solve over rows sorted by step count (n_steps [B], non-increasing, each >= 1): evaluation i
+// runs on the first rows_per_eval[i] rows (those that still have steps left; midpoint takes two evaluations per
+// step). Host only. Returns the number of evaluations S (<= cap), or a negative error.
+int rows_plan(const int* n_steps, int B, int solver, int* rows_per_eval, int cap);
 
 // -------------------------------------------------------------------------------------
 // Text encoder + duration predictor (model.py:148-535), mt_encoder.hip

@@ -9,7 +9,7 @@ from __future__ import annotations
 import math
 import numbers
 import time
-from ctypes import byref, c_char_p, c_int, c_int64, c_void_p, create_string_buffer
+from ctypes import byref, c_char_p, c_int, c_int32, c_int64, c_void_p, create_string_buffer
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -300,16 +300,25 @@ class DecoderEngine:
         check(lib().mt_decoder_set_graphs(self.h, int(bool(enable))), "decoder_set_graphs")
 
     def solve(self, packed, z_noise, temperature, mu_y, mask, spks, n_timesteps, solver="euler",
-              out=None, max_valid: int = 0, seeds=None):
+              out=None, max_valid: int = 0, seeds=None, t_span=None):
         """max_valid: the most valid frames of any utterance (synthesize's y_max), 0 when unknown. seeds (int64 [B]
         or B ints): utterance b starts from the seeded stream of seeds[b] (``seeded_noise``) drawn inside the solve,
-        z_noise is not read (pass None) and temperature is a number or one value per utterance."""
+        z_noise is not read (pass None) and temperature is a number or one value per utterance.
+        n_timesteps: an int, or one count per utterance ([B] ints); t_span: a 1-D grid of n + 1 times shared by the
+        batch or B such grids (``step_plan``). An int (or B equal ints) without t_span is the graph-replayed solve;
+        anything else is one mt_cfm_solve_rows call on the rows sorted by count, in which an utterance is left out
+        of every launch after its last step."""
         B, C, T = mu_y.shape
         s = SOLVER_EULER if solver == "euler" else SOLVER_MIDPOINT if solver == "midpoint" else None
         if s is None:
             raise NotImplementedError(f"Solver {solver} not implemented")
         if seeds is None and not is_scalar(temperature):
             raise TypeError("solve: one temperature per utterance needs seeds (or scale z_noise per row and pass 1.0)")
+        counts, grids = step_plan(n_timesteps, t_span, B)
+        if grids is not None or len(set(counts)) > 1:
+            return self._solve_rows(packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out,
+                                    max_valid, seeds)
+        n_timesteps = counts[0]
         out = torch.empty_like(mu_y) if out is None else out
         L = lib()
         nbytes = L.mt_cfm_workspace_bytes(self.h, B, T, n_timesteps, s)
@@ -326,7 +335,42 @@ class DecoderEngine:
                                      ws.data_ptr(), ws.numel(), stream_handle(mu_y.device)), "cfm_solve")
         return out
 
-    TAPS = ("down0_res", "down0_tb", "mid1_tb", "up0_out", "up1_tb")
+    def _solve_rows(self, packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out, max_valid, seeds):
+        """solve() with unequal step counts or explicit grids: the C entry point takes the rows sorted by count
+        (descending, stable), so gather them, solve, and scatter the result back to the caller's order."""
+        B, C, T = mu_y.shape
+        dev = mu_y.device
+        order = sorted(range(B), key=lambda b: -counts[b])
+        perm = None
+        if order != list(range(B)):  # from pinned memory: a pageable copy would make the host wait for the stream
+            perm = torch.tensor(order, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        take = lambda v: v if v is None or perm is None else v.index_select(0, perm)  # noqa: E731
+        sd = None if seeds is None else seed_tensor(seeds, B, dev)
+        temp = per_row(temperature, B, dev, "temperature")
+        n_max = counts[order[0]]
+        n_host = (c_int32 * B)(*[counts[b] for b in order])
+        t_host = dt_host = None
+        if grids is not None:  # [B][n_max] row-major on the host; dt = t[i + 1] - t[i] in fp32
+            t_host = torch.zeros((B, n_max), dtype=torch.float32)
+            dt_host = torch.zeros((B, n_max), dtype=torch.float32)
+            for r, b in enumerate(order):
+                t_host[r, :counts[b]] = grids[b][:-1]
+                dt_host[r, :counts[b]] = grids[b][1:] - grids[b][:-1]
+        L = lib()
+        ws = _Workspace.get(L.mt_cfm_rows_workspace_bytes(self.h, B, T, n_max, s), dev)
+        zs = torch.empty_like(mu_y) if perm is not None or out is None else out
+        # the gathered copies stay referenced until the launches are enqueued
+        g = [take(v) for v in (z_noise, sd, temp, mu_y, mask, spks)]
+        check(L.mt_cfm_solve_rows(self.h, packed.data_ptr(), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(g[4]),
+                                  ptr(g[5]), B, T, int(max_valid), n_host, ptr(t_host), ptr(dt_host), s, ptr(zs),
+                                  ws.data_ptr(), ws.numel(), stream_handle(dev)), "cfm_solve_rows")
+        if perm is None:
+            return zs
+        # `out` may be the caller's z_noise: its gathered copy was consumed by the solve, which is ahead in the stream
+        out = torch.empty_like(mu_y) if out is None else out
+        return out.index_copy_(0, perm, zs)
+
+    TAPS =("down0_res", "down0_tb", "mid1_tb", "up0_out", "up1_tb")
 
     def step_taps(self, packed, x, mu_y, mask, spks, t: float):
         """One evaluation plus the block outputs of DecoderEngine.TAPS as fp32 [B,256,T_l] (mt_decoder_set_taps)."""
@@ -496,6 +540,81 @@ def fetch_ints(t: torch.Tensor) -> List[int]:
 def is_scalar(v) -> bool:
     """a Python / numpy number or a 0-d tensor: one value for the whole batch"""
     return isinstance(v, numbers.Real) or (isinstance(v, torch.Tensor) and v.dim() == 0)
+
+
+def cosine_grid(n: int) -> torch.Tensor:
+    """The n + 1 fp32 times 1 - cos(pi/2 * i/n), i = 0..n (CPU): a t_span with small steps near t = 0. Formed in
+    fp64 and rounded once; the ends are exactly 0 and 1."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"cosine_grid: n = {n} must be >= 1")
+    i = torch.arange(n + 1, dtype=torch.float64)
+    g = (1.0 - torch.cos(i * (math.pi / 2 / n))).to(torch.float32)
+    g[0], g[-1] = 0.0, 1.0
+    return g
+
+
+def _grid(g, what: str) -> torch.Tensor:
+    """one time grid -> fp32 [n + 1] on the CPU, strictly increasing inside [0, 1]"""
+    g = torch.as_tensor(g).detach().to(device="cpu", dtype=torch.float32).contiguous()
+    if g.dim() != 1 or g.numel() < 2:
+        raise ValueError(f"{what}: a 1-D grid of n + 1 >= 2 times expected, got shape {tuple(g.shape)}")
+    if not bool(torch.isfinite(g).all()) or float(g[0]) < 0.0 or float(g[-1]) > 1.0:
+        raise ValueError(f"{what}: the times must lie inside [0, 1]")
+    if not bool((g[1:] > g[:-1]).all()):
+        raise ValueError(f"{what}: the times must be strictly increasing")
+    return g
+
+
+def step_plan(n_timesteps, t_span, B: int):
+    """solve()'s step arguments -> (counts, grids): counts a list of B ints >= 1, grids None (the reference's grid
+    i / n per utterance) or a list of B fp32 CPU grids of counts[b] + 1 times. n_timesteps: an int or one per
+    utterance ([B] tensor or sequence; None with t_span). t_span: one 1-D grid (tensor or sequence of numbers)
+    shared by the batch, or B of them (a sequence of 1-D tensors / sequences, or a [B, n + 1] tensor). Raises
+    ValueError for a wrong length, a count < 1, a grid that is not strictly increasing inside [0, 1], or counts
+    that disagree with the grids."""
+    counts = None
+    if n_timesteps is not None:
+        if is_scalar(n_timesteps):
+            counts = [int(n_timesteps)] * B
+        else:
+            nt = torch.as_tensor(n_timesteps).detach().cpu()
+            if nt.shape != (B,):
+                raise ValueError(f"n_timesteps {tuple(nt.shape)}: expected an int or one count per utterance, ({B},)")
+            if nt.dtype.is_floating_point and not bool((nt == nt.round()).all()):
+                raise ValueError("n_timesteps: whole step counts expected")
+            counts = [int(v) for v in nt.tolist()]
+            if min(counts) < 1:
+                raise ValueError(f"n_timesteps: every count must be >= 1, got {counts}")
+    if t_span is None:
+        if counts is None:
+            raise ValueError("solve: n_timesteps or t_span is needed")
+        return counts, None
+    shared = (isinstance(t_span, torch.Tensor) and t_span.dim() == 1) or (
+        not isinstance(t_span, torch.Tensor) and len(t_span) > 0 and all(is_scalar(v) for v in t_span))
+    if shared:
+        grids = [_grid(t_span, "t_span")] * B
+    else:
+        if len(t_span) != B:
+            raise ValueError(f"t_span: {len(t_span)} grids for a batch of {B} (one shared 1-D grid, or one per "
+                             "utterance)")
+        grids = [_grid(g, f"t_span[{b}]") for b, g in enumerate(t_span)]
+    steps = [g.numel() - 1 for g in grids]
+    if counts is not None and counts != steps:
+        raise ValueError(f"n_timesteps {counts} disagrees with t_span's {steps} steps")
+    return steps, grids
+
+
+def rows_plan(counts, solver: str = "euler") -> List[int]:
+    """mt_cfm_rows_plan: the rows (a prefix of the batch sorted by count, descending) each estimator evaluation of a
+    per-utterance solve runs on"""
+    n = (c_int32 * len(counts))(*[int(c) for c in counts])
+    cap = 2 * max([int(c) for c in counts] + [1])
+    rows = (c_int32 * cap)()
+    S = lib().mt_cfm_rows_plan(n, len(counts), SOLVER_MIDPOINT if solver == "midpoint" else SOLVER_EULER, rows, cap)
+    if S < 0:
+        check(S, "cfm_rows_plan")
+    return list(rows[:S])
 
 
 def per_row(v, B: int, device, name: str) -> torch.Tensor:

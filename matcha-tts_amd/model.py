@@ -434,27 +434,32 @@ class BASECFM(nn.Module):
         self.estimator = None
 
     @torch.inference_mode()
-    def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, max_valid=None, seeds=None):
+    def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, max_valid=None, seeds=None,
+                t_span=None):
         """z = randn_like(mu)*temperature, then the Euler/midpoint loop — one HIP call. max_valid (extension, not
         in the reference signature): the most valid frames of any utterance when the caller knows it (synthesize's
         y_max); it lets the solver prove every utterance padded and use the query-independent attention.
         temperature (extension): a number, or one value per utterance ([B] tensor or sequence). seeds (extension):
         int64 [B] tensor or B ints; utterance b then starts from the seeded stream of seeds[b] (rt.seeded_noise),
-        which depends on neither the batch nor the padded length, drawn inside the solve."""
+        which depends on neither the batch nor the padded length, drawn inside the solve. n_timesteps (extension):
+        also one count per utterance ([B] ints); t_span (extension): a time grid of n + 1 times in [0, 1] shared by
+        the batch, or one per utterance (rt.step_plan; rt.cosine_grid), instead of the reference's i / n."""
         rt.require_gpu(mu, mask, spks, what="CFM.forward")
         mu, mask, spks = rt.f32c(mu), rt.f32c(mask), rt.f32c(spks)
         est = self.estimator
+        kw = dict(max_valid=int(max_valid or 0), t_span=t_span)
         if seeds is not None:
-            return est.engine().solve(est.packed(mu.device), None, temperature, mu, mask, spks, int(n_timesteps),
-                                      self.solver, max_valid=int(max_valid or 0), seeds=seeds)
+            return est.engine().solve(est.packed(mu.device), None, temperature, mu, mask, spks, n_timesteps,
+                                      self.solver, seeds=seeds, **kw)
         if not rt.is_scalar(temperature):
             # unseeded, one temperature per utterance: the same draw, scaled per row here
             z = torch.randn_like(mu) * rt.per_row(temperature, mu.shape[0], mu.device, "temperature")[:, None, None]
-            return est.engine().solve(est.packed(mu.device), z, 1.0, mu, mask, spks, int(n_timesteps), self.solver,
-                                      out=z, max_valid=int(max_valid or 0))
+            return est.engine().solve(est.packed(mu.device), z, 1.0, mu, mask, spks, n_timesteps, self.solver,
+                                      out=z, **kw)
         z = torch.randn_like(mu)
-        return est.engine().solve(est.packed(mu.device), z, temperature, mu, mask, spks, int(n_timesteps),
-                                  self.solver, out=z, max_valid=int(max_valid or 0))
+        # out=z: a per-utterance solve gathers its rows first and scatters the result into z afterwards
+        return est.engine().solve(est.packed(mu.device), z, temperature, mu, mask, spks, n_timesteps,
+                                  self.solver, out=z, **kw)
 
     def compute_loss(self, x1, mask, mu, spks=None, cond=None):
         """model.py:1147-1162 -> (loss, y_t, pred, u_t): t ~ U(0,1) and z ~ N(0,1) per utterance on the
@@ -525,13 +530,17 @@ class MatchaTTS(nn.Module):
                                   "path, train_standalone.py:580-707); MatchaTTS.forward is a placeholder upstream")
 
     @torch.inference_mode()
-    def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None):
+    def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
+                   t_span=None):
         """model.py:1264-1300 -> (mel [B,80,y_max], y_lengths int64 [B], attn [B,1,Tx,T_pad]).
         Extensions for mixed batches: temperature and length_scale each take a number or one value per utterance
         ([B] tensor or sequence); seeds (int64 [B] tensor or B ints) gives utterance b the noise of seeds[b], the
-        same whatever its position, the batch, the padded length or the device (rt.seeded_noise; None: randn_like)."""
+        same whatever its position, the batch, the padded length or the device (rt.seeded_noise; None: randn_like).
+        n_timesteps takes an int or one step count per utterance, and t_span a time grid in [0, 1] shared by the
+        batch or one per utterance (n_timesteps may then be None): an utterance costs only its own steps."""
         rt.require_gpu(x, x_lengths, spks, what="MatchaTTS.synthesize")
         B = x.shape[0]
+        rt.step_plan(n_timesteps, t_span, B)  # argument errors before any launch
         if seeds is not None:
             seeds = rt.seed_tensor(seeds, B, x.device)
         if not rt.is_scalar(temperature):
@@ -553,18 +562,21 @@ class MatchaTTS(nn.Module):
                 raise IndexError("index out of range in self (a token id of x lies outside [0, n_vocab))")
             t_pad = fix_len_compatibility(y_max)
             attn, mu_y, y_mask = rt.alignment(cum, y_lengths, t_pad, mu)
-            z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max, seeds=seeds)
+            z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max, seeds=seeds,
+                             t_span=t_span)
         finally:
             est._pk.untrust()
         mel = rt.denorm_crop(z, self.mel_mean, self.mel_std, y_max)
         return mel, y_lengths, attn
 
     @torch.inference_mode()
-    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None):
+    def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
+                   t_span=None):
         """Upstream-Matcha-style alias (notebooks: MOS_audiou_generator.ipynb:294) -> dict."""
         import time
         t0 = time.perf_counter()
-        mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale, seeds)
+        mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale, seeds,
+                                               t_span)
         y_max = mel.shape[-1]
         dt = time.perf_counter() - t0
         return {"mel": mel, "mel_lengths": y_lengths, "attn": attn[:, :, :, :y_max],
