@@ -17,6 +17,8 @@
  *   mt_denoise_ragged               per call, mel cropped to its y_length: main.py:181-198,
  *                                   MOS_audiou_generator.ipynb:265-277) for a whole padded batch in one launch chain
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
+ *   mt_durations_tokens, mt_align   duration control and a forced aligner for inference: no counterpart in the
+ *                                   reference (its log-prior train_standalone.py:639-644 in direct form, textbook MAS)
  *
  * Conventions
  *  - Every pointer argument is DEVICE memory owned by the caller (PyTorch), except the
@@ -263,6 +265,15 @@ int mt_durations(const float* logw, const float* x_mask, float length_scale, int
  * mt_durations on that row with length_scale[b] */
 int mt_durations_scaled(const float* logw, const float* x_mask, const float* length_scale, int B, int Tx,
                         float* w_ceil, float* cum, int64_t* y_lengths, void* stream);
+/* Duration control. length_scale fp32 [B] (NULL: 1), token_scale fp32 [B,Tx] (NULL: 1), dur_in fp32 [B,Tx] (NULL).
+ *   dur_in == NULL: w_ceil = ceil((((exp(logw)*x_mask)*length_scale[b])*token_scale[b,x])), in that multiply order:
+ *                   with token_scale NULL or all 1 every output has the bits of mt_durations_scaled.
+ *   dur_in given:   w_ceil = dur_in*x_mask (logw may be NULL); zero-frame tokens are legal, mt_alignment skips them.
+ * cum and y_lengths as above. bad (device int32, may be NULL) is set to 0, then to 1 when an unmasked w_ceil is
+ * negative, not finite or not a whole number, or a row's sum reaches 2^24 (that row's y_length is then 1). */
+int mt_durations_tokens(const float* logw, const float* x_mask, const float* length_scale, const float* token_scale,
+                        const float* dur_in, int B, int Tx, float* w_ceil, float* cum, int64_t* y_lengths,
+                        int32_t* bad, void* stream);
 /* attn [B,1,Tx,T] one-hot path (may be NULL); mu_y[b,c,j] = mu[b,c,token(j)] [B,C,T] (may be NULL);
  * y_mask [B,1,T] = (j < y_lengths[b]) (may be NULL) */
 int mt_alignment(const float* cum, const int64_t* y_lengths, int B, int Tx, int T, const float* mu, int C,
@@ -270,6 +281,23 @@ int mt_alignment(const float* cum, const int64_t* y_lengths, int B, int Tx, int 
 /* mel[b,c,t] = z[b,c,t]*std[c] + mean[c] for t < Ty; z [B,C,T] -> mel [B,C,Ty] */
 int mt_denorm_crop(const float* z, const float* mean, const float* std, int B, int C, int T, int Ty,
                    float* mel, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Forced aligner (inference): the frames each token of mu [B,C,Tx] spans in the mel y [B,C,Ty].
+ *   log-prior, direct form, fp32, c ascending (a cell depends on mu[b,:,x] and y[b,:,j] only):
+ *     lp[b,x,j] = -0.5 * sum_c (yh[c,j] - mu[c,x])^2 - 0.5*C*log(2 pi),  yh = (y - mean)/std  (mean or std NULL: yh = y)
+ *   textbook Monotonic Alignment Search (Glow-TTS maximum_path_each; NOT mt_maximum_path's recurrence) over the
+ *   cells max(0, tx+y-ty) <= x < min(tx, y+1), NEG = -1e9:
+ *     p[x,y] = lp[x,y] + max(x == y ? NEG : p[x,y-1], x == 0 ? (y == 0 ? 0 : NEG) : p[x-1,y-1])
+ *   backtrack idx = tx-1; y = ty-1 .. 0: durations[idx] += 1; idx -= 1 when idx != 0 and
+ *     (idx == y or p[idx,y-1] < p[idx-1,y-1]).
+ * t_xs / t_ys int32 [B] are clamped to [0,Tx] / [0,Ty]; a row with t_ys < t_xs or t_xs <= 0 gets all-zero durations.
+ * durations int64 [B,Tx] (zero past t_xs); log_prior [B,Tx,Ty] and paths [B,Tx,Ty] (one-hot) may be NULL. Tx <= 1024.
+ * ------------------------------------------------------------------------------------- */
+size_t mt_align_workspace_bytes(int B, int C, int Tx, int Ty);
+int mt_align(const float* mu, const float* y, const float* mean, const float* std, const int32_t* t_xs,
+             const int32_t* t_ys, int B, int C, int Tx, int Ty, int64_t* durations, float* log_prior, float* paths,
+             void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Denoiser (hifigan/denoiser.py): STFT n_fft 1024 / hop 256 / Hann, magnitude - strength*bias,

@@ -350,6 +350,21 @@ int mt_durations_scaled(const float* logw, const float* x_mask, const float* len
   return mt::durations(logw, x_mask, 1.f, B, Tx, w_ceil, cum, (long long*)y_lengths, (hipStream_t)stream,
                        length_scale);
 }
+int mt_durations_tokens(const float* logw, const float* x_mask, const float* length_scale, const float* token_scale,
+                        const float* dur_in, int B, int Tx, float* w_ceil, float* cum, int64_t* y_lengths,
+                        int32_t* bad, void* stream) {
+  MT_REQUIRE((logw || dur_in) && x_mask && w_ceil && cum && y_lengths, "durations_tokens: null argument");
+  return mt::durations_tokens(logw, x_mask, length_scale, token_scale, dur_in, B, Tx, w_ceil, cum,
+                              (long long*)y_lengths, bad, (hipStream_t)stream);
+}
+size_t mt_align_workspace_bytes(int B, int C, int Tx, int Ty) { return mt::align_workspace_bytes(B, C, Tx, Ty); }
+int mt_align(const float* mu, const float* y, const float* mean, const float* stdv, const int32_t* t_xs,
+             const int32_t* t_ys, int B, int C, int Tx, int Ty, int64_t* durations, float* log_prior, float* paths,
+             void* ws, size_t ws_bytes, void* stream) {
+  MT_REQUIRE(mu && y && t_xs && t_ys && durations, "align: null argument");
+  return mt::align(mu, y, mean, stdv, t_xs, t_ys, B, C, Tx, Ty, (long long*)durations, log_prior, paths, ws,
+                   ws_bytes, (hipStream_t)stream);
+}
 int mt_alignment(const float* cum, const int64_t* y_lengths, int B, int Tx, int T, const float* mu, int C,
                  float* attn, float* mu_y, float* y_mask, void* stream) {
   MT_REQUIRE(cum && (mu || !mu_y) && (y_lengths || !y_mask), "alignment: null argument");

@@ -60,8 +60,17 @@ int rowdot_segs(const float* x, int ldx, const RowdotSegs& sg, float* y, int ldy
 // ls_dev (optional): one length scale per utterance, [B] in device memory, read in place of ls
 int durations(const float* logw, const float* xmask, float ls, int B, int Tx, float* w_ceil, float* cum,
               long long* ylen, hipStream_t st, const float* ls_dev = nullptr);
+// per-token scale ts [B][Tx] (optional) on top of ls_dev, or given frame counts dur_in [B][Tx] (then logw may be
+// NULL); bad (optional, device int): 1 when a count is negative / not finite / fractional or a row reaches 2^24
+int durations_tokens(const float* logw, const float* xmask, const float* ls_dev, const float* ts, const float* dur_in,
+                     int B, int Tx, float* w_ceil, float* cum, long long* ylen, int* bad, hipStream_t st);
 int alignment(const float* cum, const long long* ylen, int B, int Tx, int T, const float* mu, int C, float* attn,
               float* mu_y, float* y_mask, hipStream_t st);
+// Forced aligner (mt_align.hip): direct-form log-prior + textbook MAS -> frames per token
+size_t align_workspace_bytes(int B, int C, int Tx, int Ty);
+int align(const float* mu, const float* y, const float* mean, const float* stdv, const int* t_xs, const int* t_ys,
+          int B, int C, int Tx, int Ty, long long* durations, float* log_prior, float* paths, void* ws,
+          size_t ws_bytes, hipStream_t st);
 int denorm_crop(const float* z, const float* mean, const float* stdv, int B, int C, int T, int Ty, float* mel,
                 hipStream_t st);
 

@@ -405,18 +405,17 @@ int rowdot(const float* x, int ldx, const float* W, const float* bias, float* y,
 // duration -> alignment index path (model.py:1273-1289, 42-76). Bit-exact: every value is
 // an integer-valued fp32 (< 2^24), so sums and prefix sums are exact in any order.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void durations_kernel(const float* __restrict__ logw, const float* __restrict__ xmask,
-                                                        float ls0, const float* __restrict__ ls_dev, int Tx,
-                                                        float* __restrict__ w_ceil, float* __restrict__ cum,
-                                                        long long* __restrict__ ylen) {
+// The scan shared by the duration kernels: w_of(i) is token i's frame count (i = b * Tx + x), called once per token.
+template <class WF>
+__device__ __forceinline__ void durations_scan(WF w_of, int Tx, float* __restrict__ w_ceil, float* __restrict__ cum,
+                                               long long* __restrict__ ylen, int* __restrict__ bad) {
   // chunks of 256 * DUR_PER tokens; in a chunk thread t owns the `per` consecutive tokens [t * per, (t + 1) * per):
-  // ceil(exp(logw) * mask * ls), then an inclusive block scan of the per-thread sums (wave shuffles + one LDS pass)
+  // their frame counts, then an inclusive block scan of the per-thread sums (wave shuffles + one LDS pass)
   // on top of the previous chunks' total. Every value is an integer-valued fp32 below 2^24, so this order gives the
   // serial cumsum's bits exactly.
   constexpr int DUR_PER = 32;
   __shared__ float wsum[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const float ls = ls_dev ? ls_dev[b] : ls0;  // this utterance's length scale
   float base = 0.f;
   for (int c0 = 0; c0 < Tx; c0 += 256 * DUR_PER) {
     const int n = min(Tx - c0, 256 * DUR_PER);
@@ -429,7 +428,7 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
       w[k] = 0.f;
       if (k < per && x < c0 + n) {
         const size_t i = (size_t)b * Tx + x;
-        w[k] = ceilf((expf(logw[i]) * xmask[i]) * ls);
+        w[k] = w_of(i);
         w_ceil[i] = w[k];
         s += w[k];
       }
@@ -455,13 +454,58 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
     }
     base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
   }
-  if (tid == 255) ylen[b] = (long long)(base < 1.f ? 1.f : base);
+  if (tid != 255) return;
+  // with a flag to report it: a row of 2^24 frames or more (or a NaN sum) is past what the fp32 index path
+  // represents exactly, and gets length 1
+  const bool over = bad && !(base < 16777216.f);
+  if (over) *bad = 1;
+  ylen[b] = over ? 1 : (long long)(base < 1.f ? 1.f : base);
+}
+
+__global__ __launch_bounds__(256) void durations_kernel(const float* __restrict__ logw, const float* __restrict__ xmask,
+                                                        float ls0, const float* __restrict__ ls_dev, int Tx,
+                                                        float* __restrict__ w_ceil, float* __restrict__ cum,
+                                                        long long* __restrict__ ylen) {
+  const float ls = ls_dev ? ls_dev[blockIdx.x] : ls0;  // this utterance's length scale
+  durations_scan([=](size_t i) { return ceilf((expf(logw[i]) * xmask[i]) * ls); }, Tx, w_ceil, cum, ylen, nullptr);
+}
+
+// Per-token control: w = ceil((((exp(logw) * mask) * ls[b]) * ts[b][x])) (ls / ts NULL: 1), or, with dur_in, the given
+// frame counts w = dur_in * mask (zero-frame tokens are legal: alignment_kernel's "first x with cum[x] > j" skips
+// them). *bad (optional, zeroed by the caller) is set when an unmasked w is negative, not finite or not a whole
+// number, or a row's sum reaches 2^24.
+__global__ __launch_bounds__(256) void durations_tokens_kernel(const float* __restrict__ logw,
+                                                               const float* __restrict__ xmask,
+                                                               const float* __restrict__ ls_dev,
+                                                               const float* __restrict__ ts,
+                                                               const float* __restrict__ dur_in, int Tx,
+                                                               float* __restrict__ w_ceil, float* __restrict__ cum,
+                                                               long long* __restrict__ ylen, int* __restrict__ bad) {
+  const float ls = ls_dev ? ls_dev[blockIdx.x] : 1.f;
+  durations_scan(
+      [=](size_t i) {
+        const float m = xmask[i];
+        const float w = dur_in ? dur_in[i] * m : ceilf(((expf(logw[i]) * m) * ls) * (ts ? ts[i] : 1.f));
+        if (bad && m != 0.f && !(w >= 0.f && w < INFINITY && w == floorf(w))) *bad = 1;
+        return w;
+      },
+      Tx, w_ceil, cum, ylen, bad);
 }
 
 int durations(const float* logw, const float* xmask, float ls, int B, int Tx, float* w_ceil, float* cum,
               long long* ylen, hipStream_t st, const float* ls_dev) {
   MT_REQUIRE(B > 0 && Tx > 0, "durations: B %d, Tx %d", B, Tx);
   hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, st, logw, xmask, ls, ls_dev, Tx, w_ceil, cum, ylen);
+  MT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int durations_tokens(const float* logw, const float* xmask, const float* ls_dev, const float* ts, const float* dur_in,
+                     int B, int Tx, float* w_ceil, float* cum, long long* ylen, int* bad, hipStream_t st) {
+  MT_REQUIRE(B > 0 && Tx > 0, "durations_tokens: B %d, Tx %d", B, Tx);
+  if (bad) MT_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+  hipLaunchKernelGGL(durations_tokens_kernel, dim3(B), dim3(256), 0, st, logw, xmask, ls_dev, ts, dur_in, Tx, w_ceil,
+                     cum, ylen, bad);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -81,6 +81,9 @@ SIGNATURES = {
     "mt_vocoder_ragged_supported": (c_int, [P]),
     "mt_durations": (c_int, [P, P, c_float, c_int, c_int, P, P, P, P]),
     "mt_durations_scaled": (c_int, [P, P, P, c_int, c_int, P, P, P, P]),
+    "mt_durations_tokens": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
+    "mt_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mt_align": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     "mt_alignment": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "mt_denorm_crop": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "mt_denoise_workspace_bytes": (c_size_t, [c_int, c_int]),

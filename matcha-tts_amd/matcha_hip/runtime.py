@@ -658,15 +658,62 @@ def seeded_noise(seeds: torch.Tensor, T: int, temperature=None, C: int = 80) -> 
     return z
 
 
-def durations(logw: torch.Tensor, x_mask: torch.Tensor, length_scale):
+def _durations_exclude_scales(length_scale, token_scale) -> None:
+    if token_scale is not None or not (is_scalar(length_scale) and float(length_scale) == 1.0):
+        raise ValueError("durations replaces the duration predictor: length_scale / token_scale do not apply to it "
+                         "(scale the durations instead)")
+
+
+def duration_args(B: int, Tx: int, length_scale=1.0, token_scale=None, durations=None):
+    """synthesize's duration-control arguments, checked on the host before any launch -> (token_scale fp32 [B,Tx] |
+    None, durations fp32 [B,Tx] | None), on the devices they came from. token_scale: a [B,Tx] tensor or B sequences
+    of Tx numbers. durations: whole frames per token, an integer [B,Tx] tensor or B sequences of Tx ints; they replace
+    the predictor, so a length_scale other than the number 1 or a token_scale next to them raises ValueError."""
+    if durations is not None:
+        _durations_exclude_scales(length_scale, token_scale)
+        d = torch.as_tensor(durations).detach()
+        if d.dtype.is_floating_point or d.dtype.is_complex or d.dtype == torch.bool:
+            raise TypeError(f"durations: whole frame counts of an integer dtype expected, got {d.dtype}")
+        if d.shape != (B, Tx):
+            raise ValueError(f"durations {tuple(d.shape)}: expected one frame count per token, ({B}, {Tx})")
+        return None, d.to(torch.float32).contiguous()
+    if token_scale is None:
+        return None, None
+    ts = torch.as_tensor(token_scale).detach().to(torch.float32).contiguous()
+    if ts.shape != (B, Tx):
+        raise ValueError(f"token_scale {tuple(ts.shape)}: expected one scale per token, ({B}, {Tx})")
+    return ts, None
+
+
+def durations(logw: Optional[torch.Tensor], x_mask: torch.Tensor, length_scale=1.0, token_scale=None,
+              durations=None):
     """model.py:1273-1275 -> (w_ceil [B,1,Tx], cum [B,Tx], y_lengths int64 [B]). length_scale: a number, or one
-    per utterance ([B] tensor or sequence; mt_durations_scaled)."""
+    per utterance ([B] tensor or sequence; mt_durations_scaled).
+    Duration control (mt_durations_tokens), taken only when one of the two is given, and then the result has a fourth
+    entry, the device flag `bad` (int32 [1]: a frame count that is negative, not finite or fractional, or a row of
+    2^24 frames or more): token_scale fp32 [B,Tx] multiplies each token's predicted length before the ceil;
+    durations [B,Tx] are the frame counts themselves (logw may be None; zeros are legal)."""
     require_gpu(logw, x_mask, what="durations")
     logw, x_mask = f32c(logw), f32c(x_mask)
-    B, _, Tx = logw.shape
-    w_ceil = torch.empty((B, 1, Tx), dtype=torch.float32, device=logw.device)
-    cum = torch.empty((B, Tx), dtype=torch.float32, device=logw.device)
-    yl = torch.empty((B,), dtype=torch.int64, device=logw.device)
+    B, _, Tx = x_mask.shape
+    dev = x_mask.device
+    w_ceil = torch.empty((B, 1, Tx), dtype=torch.float32, device=dev)
+    cum = torch.empty((B, Tx), dtype=torch.float32, device=dev)
+    yl = torch.empty((B,), dtype=torch.int64, device=dev)
+    if token_scale is not None or durations is not None:
+        ts = dur = ls = None
+        if durations is not None:
+            _durations_exclude_scales(length_scale, token_scale)
+            dur = f32c(torch.as_tensor(durations).to(dev)).reshape(-1)
+        else:
+            ts = f32c(torch.as_tensor(token_scale).to(dev)).reshape(-1)
+            ls = per_row(length_scale, B, dev, "length_scale")
+        if (ts if dur is None else dur).numel() != B * Tx:
+            raise ValueError(f"token_scale / durations: expected ({B}, {Tx}) values")
+        bad = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(lib().mt_durations_tokens(ptr(logw), ptr(x_mask), ptr(ls), ptr(ts), ptr(dur), B, Tx, ptr(w_ceil),
+                                        ptr(cum), ptr(yl), ptr(bad), stream_handle(dev)), "durations_tokens")
+        return w_ceil, cum, yl, bad
     if not is_scalar(length_scale):
         ls = per_row(length_scale, B, logw.device, "length_scale")
         check(lib().mt_durations_scaled(ptr(logw), ptr(x_mask), ptr(ls), B, Tx, ptr(w_ceil), ptr(cum), ptr(yl),
@@ -750,6 +797,39 @@ def maximum_path(neg_cent: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     check(L_.mt_maximum_path(ptr(value), ptr(t_xs), ptr(t_ys), B, Tx, Ty, ptr(out), ws.data_ptr(), ws.numel(),
                              stream_handle(neg_cent.device)), "maximum_path")
     return out.to(neg_cent.dtype)
+
+
+def align(mu: torch.Tensor, y: torch.Tensor, x_lengths, y_lengths, mean=None, std=None, want_attn: bool = False,
+          want_log_prior: bool = False):
+    """Forced aligner (mt_align): mu [B,C,Tx] (the text encoder's), y [B,C,Ty] (a mel), token / frame counts [B] ->
+    (durations int64 [B,Tx], attn [B,Tx,Ty] | None, log_prior [B,Tx,Ty] | None). mean / std (a number or [C]): y is
+    a denormalized mel and is normalized first; None: y is normalized already. The log-prior is the direct form
+    -0.5 sum_c (y - mu)^2 - 0.5 C log(2 pi) in fp32 and the search the textbook MAS (Glow-TTS), not the trainer's
+    `maximum_path`. A row with y_lengths < x_lengths or no tokens gets all-zero durations."""
+    require_gpu(mu, y, what="align")
+    mu, y = f32c(mu), f32c(y)
+    B, C, Tx = mu.shape
+    if y.dim() != 3 or y.shape[0] != B or y.shape[1] != C:
+        raise ValueError(f"align: y {tuple(y.shape)} does not match mu {tuple(mu.shape)}")
+    Ty = y.shape[2]
+    dev = mu.device
+    t_xs = torch.as_tensor(x_lengths).detach().to(device=dev, dtype=torch.int32).contiguous()
+    t_ys = torch.as_tensor(y_lengths).detach().to(device=dev, dtype=torch.int32).contiguous()
+    if t_xs.shape != (B,) or t_ys.shape != (B,):
+        raise ValueError(f"align: x_lengths {tuple(t_xs.shape)} / y_lengths {tuple(t_ys.shape)}: expected ({B},)")
+    if (mean is None) != (std is None):
+        raise ValueError("align: mean and std go together")
+    if mean is not None:
+        mean = f32c(torch.as_tensor(mean).to(dev)).reshape(-1).expand(C).contiguous()
+        std = f32c(torch.as_tensor(std).to(dev)).reshape(-1).expand(C).contiguous()
+    dur = torch.empty((B, Tx), dtype=torch.int64, device=dev)
+    attn = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if want_attn else None
+    lp = torch.empty((B, Tx, Ty), dtype=torch.float32, device=dev) if want_log_prior else None
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_align_workspace_bytes(B, C, Tx, Ty), dev)
+    check(L_.mt_align(ptr(mu), ptr(y), ptr(mean), ptr(std), ptr(t_xs), ptr(t_ys), B, C, Tx, Ty, ptr(dur), ptr(lp),
+                      ptr(attn), ws.data_ptr(), ws.numel(), stream_handle(dev)), "align")
+    return dur, attn, lp
 
 
 def op_conv1d(x_btc: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor], stride=1, pad=0, dil=1,

@@ -531,15 +531,20 @@ class MatchaTTS(nn.Module):
 
     @torch.inference_mode()
     def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
-                   t_span=None):
+                   t_span=None, token_scale=None, durations=None):
         """model.py:1264-1300 -> (mel [B,80,y_max], y_lengths int64 [B], attn [B,1,Tx,T_pad]).
         Extensions for mixed batches: temperature and length_scale each take a number or one value per utterance
         ([B] tensor or sequence); seeds (int64 [B] tensor or B ints) gives utterance b the noise of seeds[b], the
         same whatever its position, the batch, the padded length or the device (rt.seeded_noise; None: randn_like).
         n_timesteps takes an int or one step count per utterance, and t_span a time grid in [0, 1] shared by the
-        batch or one per utterance (n_timesteps may then be None): an utterance costs only its own steps."""
+        batch or one per utterance (n_timesteps may then be None): an utterance costs only its own steps.
+        Duration control: token_scale (fp32 [B,Tx] or B lists) multiplies each token's predicted length before the
+        ceil; durations (integer [B,Tx] frames per token, zeros allowed) replaces the predictor, e.g. an edited
+        predict_durations() or the timing align() took from a recording. durations excludes a length_scale other
+        than 1 and token_scale; a negative count raises ValueError."""
+        B, Tx = x.shape[0], x.shape[1]
+        token_scale, durations = rt.duration_args(B, Tx, length_scale, token_scale, durations)
         rt.require_gpu(x, x_lengths, spks, what="MatchaTTS.synthesize")
-        B = x.shape[0]
         rt.step_plan(n_timesteps, t_span, B)  # argument errors before any launch
         if seeds is not None:
             seeds = rt.seed_tensor(seeds, B, x.device)
@@ -548,7 +553,12 @@ class MatchaTTS(nn.Module):
         if not rt.is_scalar(length_scale):
             length_scale = rt.per_row(length_scale, B, x.device, "length_scale")
         mu, logw, x_mask, oov = self.encoder.forward_unchecked(x, x_lengths, spks)
-        w_ceil, cum, y_lengths = rt.durations(logw, x_mask, length_scale)
+        flags = [oov[0].to(torch.int64)]
+        if token_scale is None and durations is None:
+            w_ceil, cum, y_lengths = rt.durations(logw, x_mask, length_scale)
+        else:
+            w_ceil, cum, y_lengths, bad_w = rt.durations(logw, x_mask, length_scale, token_scale, durations)
+            flags.append(bad_w[0].to(torch.int64))
         # validate the estimator's packed weights now, while the GPU runs the encoder, instead of after the
         # host sync below (nothing between here and the solve can change them)
         est = self.decoder.estimator
@@ -556,10 +566,13 @@ class MatchaTTS(nn.Module):
         est._pk.trust_next((est.precision, str(x.device)))
         try:
             # the reference's host sync (model.py:1278-1281), which also brings back the encoder's out-of-vocabulary
-            # flag (one device->host copy for both)
-            y_max, bad = rt.fetch_ints(torch.stack((y_lengths.max(), oov[0].to(torch.int64))))
+            # flag and the duration flag (one device->host copy for all)
+            y_max, bad, *bad_w = rt.fetch_ints(torch.stack([y_lengths.max()] + flags))
             if bad:
                 raise IndexError("index out of range in self (a token id of x lies outside [0, n_vocab))")
+            if bad_w and bad_w[0]:
+                raise ValueError("durations / token_scale: every token needs a whole, finite frame count >= 0 and "
+                                 "an utterance fewer than 2^24 frames")
             t_pad = fix_len_compatibility(y_max)
             attn, mu_y, y_mask = rt.alignment(cum, y_lengths, t_pad, mu)
             z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max, seeds=seeds,
@@ -571,14 +584,49 @@ class MatchaTTS(nn.Module):
 
     @torch.inference_mode()
     def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
-                   t_span=None):
+                   t_span=None, token_scale=None, durations=None):
         """Upstream-Matcha-style alias (notebooks: MOS_audiou_generator.ipynb:294) -> dict."""
         import time
         t0 = time.perf_counter()
         mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale, seeds,
-                                               t_span)
+                                               t_span, token_scale, durations)
         y_max = mel.shape[-1]
         dt = time.perf_counter() - t0
         return {"mel": mel, "mel_lengths": y_lengths, "attn": attn[:, :, :, :y_max],
                 "decoder_outputs": normalize(mel, self.mel_mean, self.mel_std),
                 "rtf": dt * 22050 / (y_max * 256)}
+
+    @torch.inference_mode()
+    def predict_durations(self, x, x_lengths, spks=None, length_scale=1.0, token_scale=None):
+        """The frames per token synthesize would use with these arguments -> int64 [B,Tx] (zero at padded tokens):
+        edit them and pass them back as synthesize(durations=...)."""
+        B, Tx = x.shape[0], x.shape[1]
+        token_scale, _ = rt.duration_args(B, Tx, length_scale, token_scale, None)
+        rt.require_gpu(x, x_lengths, spks, what="MatchaTTS.predict_durations")
+        _, logw, x_mask, oov = self.encoder.forward_unchecked(x, x_lengths, spks)
+        out = rt.durations(logw, x_mask, length_scale, token_scale)
+        rt.check_ids(oov)
+        if len(out) == 4 and rt.fetch_ints(out[3])[0]:
+            raise ValueError("token_scale: every token needs a finite frame count >= 0")
+        return out[0][:, 0].to(torch.int64)
+
+    @torch.inference_mode()
+    def align(self, x, x_lengths, mel, mel_lengths, spks=None, normalized=False, return_attn=False):
+        """Forced alignment of a mel to a text: the frames each token spans under the textbook Monotonic Alignment
+        Search on the encoder's mu (rt.align) -> durations int64 [B,Tx], with return_attn also the one-hot attn
+        [B,1,Tx,Ty]. mel [B,80,Ty] is denormalized, what synthesize returns (normalized=True: already normalized);
+        mel_lengths[b] >= x_lengths[b] (every token takes at least one frame). synthesize(durations=...) then speaks
+        the text with the recording's timing."""
+        rt.require_gpu(x, x_lengths, mel, spks, what="MatchaTTS.align")
+        xl = torch.as_tensor(x_lengths).detach().cpu().to(torch.int64)
+        yl = torch.as_tensor(mel_lengths).detach().cpu().to(torch.int64)
+        if xl.shape != (x.shape[0],) or yl.shape != xl.shape:
+            raise ValueError(f"align: x_lengths {tuple(xl.shape)} / mel_lengths {tuple(yl.shape)}: one per utterance")
+        if bool((yl < xl).any()) or int(yl.max()) > mel.shape[-1]:
+            raise ValueError(f"align: mel_lengths {yl.tolist()} must cover x_lengths {xl.tolist()} (a frame per "
+                             f"token) and fit the mel's {mel.shape[-1]} frames")
+        mu, _, _, oov = self.encoder.forward_unchecked(x, x_lengths, spks)
+        mean, std = (None, None) if normalized else (self.mel_mean, self.mel_std)
+        dur, attn, _ = rt.align(mu, mel, xl, yl, mean, std, want_attn=return_attn)
+        rt.check_ids(oov)
+        return (dur, attn.unsqueeze(1)) if return_attn else dur
