@@ -173,6 +173,24 @@ int mt_cfm_solve_rows(const mt_decoder* d, const void* packed, const float* z_no
                       const float* temperature, const float* mu_y, const float* mask, const float* spks, int B, int T,
                       int max_valid, const int32_t* n_steps, const float* t, const float* dt, int solver, float* z_out,
                       void* ws, size_t ws_bytes, void* stream);
+/* Mel infill: mt_cfm_solve_rows with some frames given. x1 (fp32 [B,80,T], device, normalized mel) and keep (uint8
+ * [B,T], device, non-zero = kept); a frame is kept only where mask != 0 too, padded frames are never written. Kept
+ * frames are held on the training-time conditional path p(t) = (1 - (1 - sigma_min) t) z0 + t x1 in fp32 (model.py:
+ * 1147-1162), z0 the utterance's own initial noise (seeded, or z_noise times temperature), p(1) = x1 itself: before
+ * evaluation 0 state and estimator input are p(t_0); after an Euler step or a midpoint second evaluation both are
+ * p(t_{i+1}); after a midpoint first half the estimator input alone is p(t_i + dt_i / 2). Free frames are integrated
+ * as in mt_cfm_solve_rows and see the kept ones through the estimator. One extra element-wise launch
+ * (infill_clamp_kernel) per evaluation on the rows still in the batch, and one before the first. t: whole grids, fp32
+ * [B][n_steps[0] + 1] row-major on the host, row b strictly increasing inside [0, 1] over its first n_steps[b] + 1
+ * entries (dt_i = t[i+1] - t[i] in fp32; the clamp takes t[i+1] itself), or NULL: the reference grid (float)(i / n_b).
+ * sigma_min in [0, 1). Every other argument, check and message as mt_cfm_solve_rows. Workspace:
+ * mt_cfm_infill_workspace_bytes(d, B, T, n_steps[0], solver). */
+size_t mt_cfm_infill_workspace_bytes(const mt_decoder* d, int B, int T, int n_max, int solver);
+int mt_cfm_solve_infill(const mt_decoder* d, const void* packed, const float* z_noise, const int64_t* seeds,
+                        const float* temperature, const float* mu_y, const float* mask, const float* spks,
+                        const float* x1, const uint8_t* keep, float sigma_min, int B, int T, int max_valid,
+                        const int32_t* n_steps, const float* t, int solver, float* z_out, void* ws, size_t ws_bytes,
+                        void* stream);
 /* Seeded Gaussian noise, z [B,C,T] fp32 (C % 4 == 0): z[b,c,t] depends on (seeds[b], c, t) only, not on B, T or the
  * row's position. Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) of the int64 seed's two's-complement uint64
  * on the counter (t, c / 4, 0, 0); each output word x gives u(x) = (2 (x >> 9) + 1) 2^-24; channels 4q, 4q + 1 are

@@ -217,6 +217,29 @@ int mt_cfm_solve_rows(const mt_decoder* d, const void* packed, const float* z_no
   return d->d.solve_rows(packed, z_noise, (const long long*)seeds, temperature, mu_y, mask, spks, B, T, max_valid,
                          n_steps, t, dt, solver, z_out, ws, ws_bytes, (hipStream_t)stream);
 }
+size_t mt_cfm_infill_workspace_bytes(const mt_decoder* d, int B, int T, int n_max, int solver) {
+  if (!d || B <= 0 || T <= 0 || n_max <= 0) return 0;
+  return d->d.infill_workspace_bytes(B, T, solver == 1 ? 2 * n_max : n_max);
+}
+int mt_cfm_solve_infill(const mt_decoder* d, const void* packed, const float* z_noise, const int64_t* seeds,
+                        const float* temperature, const float* mu_y, const float* mask, const float* spks,
+                        const float* x1, const uint8_t* keep, float sigma_min, int B, int T, int max_valid,
+                        const int32_t* n_steps, const float* t, int solver, float* z_out, void* ws, size_t ws_bytes,
+                        void* stream) {
+  MT_REQUIRE(d, "cfm_solve_infill: decoder is NULL");
+  MT_REQUIRE(packed, "cfm_solve_infill: packed is NULL");
+  MT_REQUIRE(z_noise || seeds, "cfm_solve_infill: z_noise and seeds are both NULL (give one)");
+  MT_REQUIRE(!(z_noise && seeds), "cfm_solve_infill: z_noise and seeds are both given (give one)");
+  MT_REQUIRE(mu_y, "cfm_solve_infill: mu_y is NULL");
+  MT_REQUIRE(mask, "cfm_solve_infill: mask is NULL");
+  MT_REQUIRE(x1, "cfm_solve_infill: x1 is NULL");
+  MT_REQUIRE(keep, "cfm_solve_infill: keep is NULL");
+  MT_REQUIRE(n_steps, "cfm_solve_infill: n_steps is NULL");
+  MT_REQUIRE(z_out, "cfm_solve_infill: z_out is NULL");
+  MT_REQUIRE(ws, "cfm_solve_infill: workspace is NULL");
+  return d->d.solve_infill(packed, z_noise, (const long long*)seeds, temperature, mu_y, mask, spks, x1, keep, sigma_min,
+                           B, T, max_valid, n_steps, t, solver, z_out, ws, ws_bytes, (hipStream_t)stream);
+}
 int mt_noise_fill(const int64_t* seeds, const float* temperature, int B, int C, int T, float* z, void* stream) {
   MT_REQUIRE(seeds, "noise_fill: seeds is NULL");
   MT_REQUIRE(z, "noise_fill: z is NULL");

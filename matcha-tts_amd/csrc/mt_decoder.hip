@@ -1150,10 +1150,14 @@ size_t Decoder::rows_workspace_bytes(int B, int T, int S) const {
   return workspace_bytes(B, T, S * B) + align256(3 * SB * 4) + align256(SB * n_res * C * 4);
 }
 
+size_t Decoder::infill_workspace_bytes(int B, int T, int S) const {
+  return rows_workspace_bytes(B, T, S) + 2 * align256((size_t)B * T * NF * 4) + align256((size_t)(S + 1) * B * 4);
+}
+
 int Decoder::solve_rows(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
                         const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
                         const int* n_steps, const float* t, const float* dt, int solver, float* z_out, void* ws,
-                        size_t ws_bytes, hipStream_t st) const {
+                        size_t ws_bytes, hipStream_t st, const Infill* infill) const {
   int rc;
   if ((rc = check_geom(B, T))) return rc;
   MT_REQUIRE(solver == 0 || solver == 1, "cfm: solver must be 0 (euler) or 1 (midpoint)");
@@ -1164,8 +1168,8 @@ int Decoder::solve_rows(const void* packed, const float* z_noise, const long lon
   std::vector<int> rows((size_t)per * n_max);
   const int S = rows_plan(n_steps, B, solver, rows.data(), (int)rows.size());
   if (S < 0) return S;
-  MT_REQUIRE(ws_bytes >= rows_workspace_bytes(B, T, S), "cfm_solve_rows: workspace %zu < %zu", ws_bytes,
-             rows_workspace_bytes(B, T, S));
+  const size_t ws_need = infill ? infill_workspace_bytes(B, T, S) : rows_workspace_bytes(B, T, S);
+  MT_REQUIRE(ws_bytes >= ws_need, "cfm_solve_rows: workspace %zu < %zu", ws_bytes, ws_need);
   MT_REQUIRE(max_valid >= 0 && max_valid <= T, "cfm: max_valid %d outside [0, T=%d]", max_valid, T);
   const char* P = (const char*)packed;
   Work w = carve(ws, B, T, S * B);
@@ -1180,6 +1184,9 @@ int Decoder::solve_rows(const void* packed, const float* z_noise, const long lon
   // evaluation (step 0, index 0).
   const size_t SB = (size_t)S * B;
   std::vector<unsigned> ut, hd(SB, 0u), hi(SB, 0u);
+  // infill: the [S + 1][B] clamp times, row 0 before evaluation 0 (t_0), row ev + 1 after evaluation ev: the time the
+  // estimator input then stands at (a midpoint first half: t_i + dt_i / 2; else t_{i+1}, the grid value itself)
+  std::vector<unsigned> hc(infill ? SB + B : 0, 0u);
   std::unordered_map<unsigned, int> seen;
   auto bits = [](float v) {
     unsigned u;
@@ -1209,6 +1216,17 @@ int Decoder::solve_rows(const void* packed, const float* z_noise, const long lon
         put(2 * i, b, ti, di);
         put(2 * i + 1, b, ti + di * 0.5f, di);
       }
+      if (infill) {
+        const float tn = infill->grid ? infill->grid[(size_t)b * (n_max + 1) + i + 1]
+                                      : (float)((double)(i + 1) / (double)n_steps[b]);
+        if (i == 0) hc[b] = bits(ti);
+        if (solver == 0) {
+          hc[(size_t)(i + 1) * B + b] = bits(tn);
+        } else {
+          hc[(size_t)(2 * i + 1) * B + b] = bits(ti + di * 0.5f);
+          hc[(size_t)(2 * i + 2) * B + b] = bits(tn);
+        }
+      }
     }
   }
   const size_t U = ut.size();  // 1 <= U <= SB
@@ -1221,14 +1239,34 @@ int Decoder::solve_rows(const void* packed, const float* z_noise, const long lon
   const float* dt_tab = (const float*)(dev_tab + U);
   const int* idx_tab = (const int*)(dev_tab + U + SB);
   float* tb_rows = (float*)((char*)dev_tab + align256(3 * SB * 4));
-  for (size_t o = 0; o < tab.size(); o += TablePiece::N) {
-    TablePiece pc;
-    const int n = (int)std::min((size_t)TablePiece::N, tab.size() - o);
-    std::copy(tab.begin() + (long)o, tab.begin() + (long)o + n, pc.v);
-    hipLaunchKernelGGL(table_piece_kernel, dim3((TablePiece::N + 255) / 256), dim3(256), 0, st, pc, dev_tab + o, n);
-    MT_CHECK_HIP(hipGetLastError());
-  }
+  auto upload = [&](const std::vector<unsigned>& src, unsigned* dst) {
+    for (size_t o = 0; o < src.size(); o += TablePiece::N) {
+      TablePiece pc;
+      const int n = (int)std::min((size_t)TablePiece::N, src.size() - o);
+      std::copy(src.begin() + (long)o, src.begin() + (long)o + n, pc.v);
+      hipLaunchKernelGGL(table_piece_kernel, dim3((TablePiece::N + 255) / 256), dim3(256), 0, st, pc, dst + o, n);
+      MT_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+  };
+  if ((rc = upload(tab, dev_tab))) return rc;
   if ((rc = init_inputs(w, z_noise, 1.f, mu_y, spks, B, T, st, seeds, temp_dev))) return rc;
+  // infill, behind the rows workspace: z0 (the master as init_inputs left it) and x1 as [B][T][80] fp32, the clamp times
+  const size_t zbytes = (size_t)B * T * NF * 4;
+  float* z0 = (float*)((char*)ws + rows_workspace_bytes(B, T, S));
+  float* x1t = (float*)((char*)z0 + align256(zbytes));
+  const float* tc = (const float*)((char*)x1t + align256(zbytes));
+  const float one_m_sigma = infill ? (float)(1.0 - (double)infill->sigma_min) : 0.f;
+  auto clamp = [&](int row, int nrows, int update_master) {
+    return infill_clamp(dtype, z0, x1t, infill->keep, mask, tc + (size_t)row * B, one_m_sigma, nrows, T, update_master,
+                        w.zm, w.xin, xld(), st);
+  };
+  if (infill) {
+    if ((rc = upload(hc, (unsigned*)tc))) return rc;
+    MT_CHECK_HIP(hipMemcpyAsync(z0, w.zm, zbytes, hipMemcpyDeviceToDevice, st));
+    if ((rc = bct_to_btc(F32, infill->x1, B, NF, T, 1.f, x1t, NF, 0, st))) return rc;
+    if ((rc = clamp(0, B, 1))) return rc;  // state and input at p(t_0): the identity when t_0 = 0
+  }
   // the time embedding and every ResnetBlock's time bias per distinct time into w.tb [U][n_res * C], then laid out
   // per (evaluation, utterance)
   if ((rc = time_embed(P, w, TimeSched{}, (int)U, st, t_uniq))) return rc;
@@ -1240,8 +1278,46 @@ int Decoder::solve_rows(const void* packed, const float* z_noise, const long lon
     Euler eu{0.f, solver == 1 && i % 2 == 0, solver == 0 || i % 2 == 1, dt_tab + (size_t)i * B};
     rc = dtype == BF16 ? eval<bf16>(P, wi, rows[i], T, i, eu, st) : eval<float>(P, wi, rows[i], T, i, eu, st);
     if (rc) return rc;
+    // a launch of its own: the two Euler epilogues stay as they are (bit-identity contracts)
+    if (infill && (rc = clamp(i + 1, rows[i], eu.update_master))) return rc;
   }
   return btc_to_bct(F32, w.zm, NF, 0, B, NF, T, z_out, st);
+}
+
+int Decoder::solve_infill(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
+                          const float* mu_y, const float* mask, const float* spks, const float* x1,
+                          const unsigned char* keep, float sigma_min, int B, int T, int max_valid, const int* n_steps,
+                          const float* grid, int solver, float* z_out, void* ws, size_t ws_bytes,
+                          hipStream_t st) const {
+  MT_REQUIRE(sigma_min >= 0.f && sigma_min < 1.f, "cfm_solve_infill: sigma_min %g outside [0, 1)", (double)sigma_min);
+  MT_REQUIRE(B > 0 && n_steps, "cfm_solve_infill: empty batch or n_steps is NULL");
+  MT_REQUIRE(solver == 0 || solver == 1, "cfm: solver must be 0 (euler) or 1 (midpoint)");
+  MT_REQUIRE(n_steps[0] >= 1 && n_steps[0] <= kRowsMaxSteps, "cfm_solve_rows: n_steps[0] = %d outside [1, %d]",
+             n_steps[0], kRowsMaxSteps);
+  const int n_max = n_steps[0];
+  {  // sorted counts, each >= 1, before a grid row is indexed by them
+    std::vector<int> rows((size_t)2 * n_max);
+    const int S = rows_plan(n_steps, B, solver, rows.data(), (int)rows.size());
+    if (S < 0) return S;
+  }
+  const Infill inf{x1, keep, sigma_min, grid};
+  if (!grid)
+    return solve_rows(packed, z_noise, seeds, temp_dev, mu_y, mask, spks, B, T, max_valid, n_steps, nullptr, nullptr,
+                      solver, z_out, ws, ws_bytes, st, &inf);
+  std::vector<float> tv((size_t)B * n_max, 0.f), dv((size_t)B * n_max, 0.f);
+  for (int b = 0; b < B; ++b) {
+    const float* g = grid + (size_t)b * (n_max + 1);
+    MT_REQUIRE(g[0] >= 0.f && g[n_steps[b]] <= 1.f, "cfm_solve_infill: grid row %d [%g, %g] outside [0, 1]", b,
+               (double)g[0], (double)g[n_steps[b]]);
+    for (int i = 0; i < n_steps[b]; ++i) {
+      MT_REQUIRE(g[i + 1] > g[i], "cfm_solve_infill: grid row %d is not strictly increasing at step %d (%g then %g)", b,
+                 i, (double)g[i], (double)g[i + 1]);
+      tv[(size_t)b * n_max + i] = g[i];
+      dv[(size_t)b * n_max + i] = g[i + 1] - g[i];  // in fp32, as DecoderEngine._solve_rows forms it
+    }
+  }
+  return solve_rows(packed, z_noise, seeds, temp_dev, mu_y, mask, spks, B, T, max_valid, n_steps, tv.data(), dv.data(),
+                    solver, z_out, ws, ws_bytes, st, &inf);
 }
 
 }  // namespace mt

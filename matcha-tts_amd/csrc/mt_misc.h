@@ -34,6 +34,17 @@ int copy_rows(int dtype, const void* src, int ld_src, int rows, int C, void* dst
 // x[r][c] *= mask[r]
 int mask_rows(int dtype, void* x, int rows, int C, const float* mask, hipStream_t st);
 
+// Mel infill: the kept frames of the first `rows` utterances are set to the conditional path
+// p = (1 - (1 - sigma_min) t) z0 + t x1 (p = x1 itself at t == 1) at t = t_rows[b]: the fp32 master zm [B][T][80]
+// (only when update_master) and columns 0 .. 79 of the estimator input xin [B][T][ld] (element type by dtype, p * mask).
+// z0, x1: fp32 [B][T][80]; keep: uint8 [B][T]; a frame is kept when keep != 0 and mask != 0, so padded frames are
+// neither read nor written. one_m_sigma = 1 - sigma_min. ld % 4 == 0. One launch of infill_clamp_kernel.
+int infill_clamp(int dtype, const float* z0, const float* x1, const unsigned char* keep, const float* mask,
+                 const float* t_rows, float one_m_sigma, int rows, int T, int update_master, float* zm, void* xin,
+                 int ld, hipStream_t st);
+// launch-log tag of infill_clamp (the record's ef field, family VCLOG_CONV like proj_euler's; B = rows, L = T)
+enum : int { INFILL_LOG = 0x1000000 };
+
 // ResnetBlock1D block tail (GroupNorm(8) -> Mish [-> + time bias] -> * mask, model.py Block1D/ResnetBlock1D)
 // for bf16 rows y[b][t][C] whose GroupNorm partial sums (fp64 (sum, sumsq) per (b, 32-channel group,
 // part), nparts per group) a conv epilogue produced: h = (mish(y * ga[b,c] + gs[b,c]) + tb[c]) * mask[b,t]

@@ -4,6 +4,8 @@
 
 #include <algorithm>
 
+#include "mt_probe.h"
+
 namespace mt {
 
 // ------------------------------------------------------------------------------------
@@ -610,6 +612,75 @@ int mask_rows(int dtype, void* x, int rows, int C, const float* mask, hipStream_
   else
     hipLaunchKernelGGL(mask_rows_kernel<float>, dim3(blocks), dim3(256), 0, st, (float*)x, rows, C, mask);
   MT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// mel infill: kept frames onto the conditional path p(t) = (1 - (1 - sigma_min) t) z0 + t x1
+// ------------------------------------------------------------------------------------
+// Element-wise over [rows][T][80], a thread per 4 channels of a frame (20 threads per frame). Each product and the sum
+// are rounded on their own (no FMA contraction), so p is the fp32 expression as written whatever the compiler does.
+template <class E>
+__global__ __launch_bounds__(256) void infill_clamp_kernel(const float* __restrict__ z0, const float* __restrict__ x1,
+                                                           const unsigned char* __restrict__ keep,
+                                                           const float* __restrict__ mask,
+                                                           const float* __restrict__ t_rows, float one_m_sigma,
+                                                           unsigned frames, int T, int update_master,
+                                                           float* __restrict__ zm, E* __restrict__ xin, int ld) {
+  constexpr unsigned Q = 80 / 4;
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  const unsigned fr = i / Q, q = i - fr * Q;  // fr = b * T + frame
+  if (fr >= frames) return;
+  const float m = mask[fr];
+  // keep_eff = keep && mask != 0: a padded frame is never written here, whatever the caller's keep says. Its xin slot
+  // stays 0 and its master stays as init_inputs left it, which the stored-masked xin of the vconv path and the o_b
+  // kept over a solve (DECK_OVEC) rest on.
+  if (keep[fr] == 0 || m == 0.f) return;
+  const float t = t_rows[fr / (unsigned)T];
+  const size_t e = (size_t)fr * 80 + 4 * q;
+  const f32x4 xv = *reinterpret_cast<const f32x4*>(x1 + e);
+  f32x4 p = xv;  // p(1) is x1 itself
+  if (t != 1.0f) {
+    const f32x4 zv = *reinterpret_cast<const f32x4*>(z0 + e);
+    const float a = __fsub_rn(1.0f, __fmul_rn(one_m_sigma, t));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r] = __fadd_rn(__fmul_rn(a, zv[r]), __fmul_rn(t, xv[r]));
+  }
+  if (update_master) *reinterpret_cast<f32x4*>(zm + e) = p;
+  E* xz = xin + (size_t)fr * ld + 4 * q;
+  if constexpr (sizeof(E) == 2) {
+    bf16x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = (bf16)(p[r] * m);
+    *reinterpret_cast<bf16x4*>(xz) = o;
+  } else {
+    f32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = p[r] * m;
+    *reinterpret_cast<f32x4*>(xz) = o;
+  }
+}
+
+int infill_clamp(int dtype, const float* z0, const float* x1, const unsigned char* keep, const float* mask,
+                 const float* t_rows, float one_m_sigma, int rows, int T, int update_master, float* zm, void* xin,
+                 int ld, hipStream_t st) {
+  MT_REQUIRE(z0 && x1 && keep && mask && t_rows && zm && xin, "infill_clamp: null pointer");
+  MT_REQUIRE(rows > 0 && T > 0 && (long long)rows * T * 20 < (1ll << 31), "infill_clamp: %d rows of %d frames", rows, T);
+  const size_t ebytes = dtype == BF16 ? 2 : 4;
+  MT_REQUIRE(ld >= 80 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(xin) & (4 * ebytes - 1)) == 0 &&
+                 ((reinterpret_cast<uintptr_t>(zm) | reinterpret_cast<uintptr_t>(z0) | reinterpret_cast<uintptr_t>(x1)) &
+                  15) == 0,
+             "infill_clamp: row stride %d / alignment", ld);
+  const unsigned frames = (unsigned)rows * (unsigned)T, blocks = (frames * 20u + 255u) / 256u;
+  if (dtype == BF16)
+    hipLaunchKernelGGL(infill_clamp_kernel<bf16>, dim3(blocks), dim3(256), 0, st, z0, x1, keep, mask, t_rows,
+                       one_m_sigma, frames, T, update_master, zm, (bf16*)xin, ld);
+  else
+    hipLaunchKernelGGL(infill_clamp_kernel<float>, dim3(blocks), dim3(256), 0, st, z0, x1, keep, mask, t_rows,
+                       one_m_sigma, frames, T, update_master, zm, (float*)xin, ld);
+  MT_CHECK_HIP(hipGetLastError());
+  const int rec[VCLOG_FIELDS] = {INFILL_LOG, 80, 0, 1, (int)blocks, (int)blocks, 1, 80, 80, rows, T};
+  vclog_record(rec);
   return 0;
 }
 

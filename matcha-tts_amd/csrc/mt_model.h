@@ -172,18 +172,36 @@ struct Decoder {
             const float* mask, const float* spks, int B, int T, int n_steps, int solver, float* z_out,
             void* ws, size_t ws_bytes, hipStream_t st, int max_valid = 0, const long long* seeds = nullptr,
             const float* temp_dev = nullptr) const;
+  // Mel infill (mt_cfm_solve_infill): solve_rows with the kept frames held on the conditional path
+  // p(t) = (1 - (1 - sigma_min) t) z0 + t x1, z0 the master right after init_inputs. x1 fp32 [B,80,T] (normalized) and
+  // keep uint8 [B,T] in device memory; grid: host [B][n_steps[0] + 1] (the times solve_rows' t / dt were formed from;
+  // the clamp after step i takes grid[b][i + 1] itself) or null for the reference grid, where it is (float)((i + 1) / n_b).
+  struct Infill {
+    const float* x1;
+    const unsigned char* keep;
+    float sigma_min;
+    const float* grid;
+  };
   // One solve with a step count and a time grid per utterance (mt_cfm_solve_rows). Rows sorted by n_steps
   // (host, [B], non-increasing); t / dt (host, [B][n_steps[0]] row-major, or both null: the reference grid i / n_b
   // with dt = 1 / n_b). Evaluation i runs on the first rows_plan()[i] rows only, launched directly on st (no graph);
-  // a row's master is what its last update stored. The host arrays are consumed before the call returns.
+  // a row's master is what its last update stored. The host arrays are consumed before the call returns. infill
+  // (optional): the kept frames are clamped to the path before evaluation 0 and after every evaluation.
   int solve_rows(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
                  const float* mu_y, const float* mask, const float* spks, int B, int T, int max_valid,
                  const int* n_steps, const float* t, const float* dt, int solver, float* z_out, void* ws,
-                 size_t ws_bytes, hipStream_t st) const;
+                 size_t ws_bytes, hipStream_t st, const Infill* infill = nullptr) const;
   // workspace of solve_rows: the shared-time workspace with room for S * B distinct times, the [S][B] step / index tables
   // and the [S][B][n_res * C] per-utterance time biases
   size_t rows_workspace_bytes(int B, int T, int S) const;
   static constexpr int kRowsMaxSteps = 1024;  // per utterance (solve_rows)
+  // mt_cfm_solve_infill: solve_rows' checks, then the grid's (each row strictly increasing inside [0, 1]); t / dt are formed from the grid
+  int solve_infill(const void* packed, const float* z_noise, const long long* seeds, const float* temp_dev,
+                   const float* mu_y, const float* mask, const float* spks, const float* x1, const unsigned char* keep,
+                   float sigma_min, int B, int T, int max_valid, const int* n_steps, const float* grid, int solver,
+                   float* z_out, void* ws, size_t ws_bytes, hipStream_t st) const;
+  // rows_workspace_bytes plus z0 and the transposed x1 ([B][T][80] fp32 each) and the [S + 1][B] clamp times
+  size_t infill_workspace_bytes(int B, int T, int S) const;
   // 1 (default): the query-independent attention path when the caller's max_valid allows it; 0: always the
   // general Q.K^T path (A/B, tests)
   int uniform_attn = 1;

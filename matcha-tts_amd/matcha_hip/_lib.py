@@ -56,6 +56,9 @@ SIGNATURES = {
     "mt_cfm_rows_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int, c_int]),
     "mt_cfm_rows_plan": (c_int, [P, c_int, c_int, P, c_int]),
     "mt_cfm_solve_rows": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
+    "mt_cfm_infill_workspace_bytes": (c_size_t, [P, c_int, c_int, c_int, c_int]),
+    "mt_cfm_solve_infill": (c_int, [P, P, P, P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, P, P, c_int, P, P,
+                                    c_size_t, P]),
     "mt_noise_fill": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "mt_decoder_set_uniform_attention": (c_int, [P, c_int]),
     "mt_decoder_set_graphs": (c_int, [P, c_int]),

@@ -300,21 +300,30 @@ class DecoderEngine:
         check(lib().mt_decoder_set_graphs(self.h, int(bool(enable))), "decoder_set_graphs")
 
     def solve(self, packed, z_noise, temperature, mu_y, mask, spks, n_timesteps, solver="euler",
-              out=None, max_valid: int = 0, seeds=None, t_span=None):
+              out=None, max_valid: int = 0, seeds=None, t_span=None, x1=None, keep=None, sigma_min: float = 1e-4):
         """max_valid: the most valid frames of any utterance (synthesize's y_max), 0 when unknown. seeds (int64 [B]
         or B ints): utterance b starts from the seeded stream of seeds[b] (``seeded_noise``) drawn inside the solve,
         z_noise is not read (pass None) and temperature is a number or one value per utterance.
         n_timesteps: an int, or one count per utterance ([B] ints); t_span: a 1-D grid of n + 1 times shared by the
         batch or B such grids (``step_plan``). An int (or B equal ints) without t_span is the graph-replayed solve;
         anything else is one mt_cfm_solve_rows call on the rows sorted by count, in which an utterance is left out
-        of every launch after its last step."""
+        of every launch after its last step.
+        Mel infill: x1 (fp32 [B,80,T], normalized) with keep ([B,T] or [B,1,T], bool or numeric, non-zero = kept)
+        holds the kept valid frames on the path (1 - (1 - sigma_min) t) z0 + t x1 while the others are integrated
+        (``infill_args``); they come back as x1's bits. Every such call is one mt_cfm_solve_infill call on the sorted
+        rows, also with one shared count: the graph path has no infill."""
         B, C, T = mu_y.shape
+        x1, keep = infill_args(x1, keep, B, C, T, sigma_min)
         s = SOLVER_EULER if solver == "euler" else SOLVER_MIDPOINT if solver == "midpoint" else None
         if s is None:
             raise NotImplementedError(f"Solver {solver} not implemented")
         if seeds is None and not is_scalar(temperature):
             raise TypeError("solve: one temperature per utterance needs seeds (or scale z_noise per row and pass 1.0)")
         counts, grids = step_plan(n_timesteps, t_span, B)
+        if x1 is not None:
+            require_gpu(mu_y, x1, keep, what="DecoderEngine.solve")
+            return self._solve_rows(packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out,
+                                    max_valid, seeds, (f32c(x1.to(mu_y.device)), keep.to(mu_y.device), float(sigma_min)))
         if grids is not None or len(set(counts)) > 1:
             return self._solve_rows(packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out,
                                     max_valid, seeds)
@@ -335,9 +344,11 @@ class DecoderEngine:
                                      ws.data_ptr(), ws.numel(), stream_handle(mu_y.device)), "cfm_solve")
         return out
 
-    def _solve_rows(self, packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out, max_valid, seeds):
+    def _solve_rows(self, packed, z_noise, temperature, mu_y, mask, spks, counts, grids, s, out, max_valid, seeds,
+                    infill=None):
         """solve() with unequal step counts or explicit grids: the C entry point takes the rows sorted by count
-        (descending, stable), so gather them, solve, and scatter the result back to the caller's order."""
+        (descending, stable), so gather them, solve, and scatter the result back to the caller's order. infill:
+        (x1 fp32 [B,80,T], keep uint8 [B,T], sigma_min) -> mt_cfm_solve_infill, which takes whole grids."""
         B, C, T = mu_y.shape
         dev = mu_y.device
         order = sorted(range(B), key=lambda b: -counts[b])
@@ -357,8 +368,24 @@ class DecoderEngine:
                 t_host[r, :counts[b]] = grids[b][:-1]
                 dt_host[r, :counts[b]] = grids[b][1:] - grids[b][:-1]
         L = lib()
-        ws = _Workspace.get(L.mt_cfm_rows_workspace_bytes(self.h, B, T, n_max, s), dev)
         zs = torch.empty_like(mu_y) if perm is not None or out is None else out
+        if infill is not None:
+            g_host = None
+            if grids is not None:  # [B][n_max + 1]: the clamp after step i takes t[i + 1] itself
+                g_host = torch.zeros((B, n_max + 1), dtype=torch.float32)
+                for r, b in enumerate(order):
+                    g_host[r, :counts[b] + 1] = grids[b]
+            ws = _Workspace.get(L.mt_cfm_infill_workspace_bytes(self.h, B, T, n_max, s), dev)
+            g = [take(v) for v in (z_noise, sd, temp, mu_y, mask, spks, infill[0], infill[1])]
+            check(L.mt_cfm_solve_infill(self.h, packed.data_ptr(), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]),
+                                        ptr(g[4]), ptr(g[5]), ptr(g[6]), ptr(g[7]), infill[2], B, T, int(max_valid),
+                                        n_host, ptr(g_host), s, ptr(zs), ws.data_ptr(), ws.numel(),
+                                        stream_handle(dev)), "cfm_solve_infill")
+            if perm is None:
+                return zs
+            out = torch.empty_like(mu_y) if out is None else out
+            return out.index_copy_(0, perm, zs)
+        ws = _Workspace.get(L.mt_cfm_rows_workspace_bytes(self.h, B, T, n_max, s), dev)
         # the gathered copies stay referenced until the launches are enqueued
         g = [take(v) for v in (z_noise, sd, temp, mu_y, mask, spks)]
         check(L.mt_cfm_solve_rows(self.h, packed.data_ptr(), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(g[4]),
@@ -603,6 +630,29 @@ def step_plan(n_timesteps, t_span, B: int):
     if counts is not None and counts != steps:
         raise ValueError(f"n_timesteps {counts} disagrees with t_span's {steps} steps")
     return steps, grids
+
+
+def infill_args(x1, keep, B: int, C: int, T: int, sigma_min: float = 1e-4):
+    """solve()'s infill arguments, checked on the host before any launch -> (x1, keep uint8 [B,T] contiguous) on the
+    devices they came from, or (None, None). x1: a floating [B,C,T] tensor; keep: bool or numeric [B,T] or [B,1,T],
+    non-zero = kept. One without the other, a wrong shape or a sigma_min outside [0, 1) raises ValueError, a
+    non-tensor or a non-floating x1 / complex keep TypeError."""
+    if x1 is None and keep is None:
+        return None, None
+    if x1 is None or keep is None:
+        raise ValueError("infill: x1 and keep come together (%s is missing)" % ("x1" if x1 is None else "keep"))
+    if not isinstance(x1, torch.Tensor) or not x1.dtype.is_floating_point:
+        raise TypeError("infill: x1 is a floating-point [B,C,T] tensor")
+    keep = torch.as_tensor(keep)
+    if keep.dtype.is_complex:
+        raise TypeError(f"infill: keep is bool or numeric, got {keep.dtype}")
+    if tuple(x1.shape) != (B, C, T):
+        raise ValueError(f"infill: x1 {tuple(x1.shape)}: expected ({B}, {C}, {T})")
+    if tuple(keep.shape) not in ((B, T), (B, 1, T)):
+        raise ValueError(f"infill: keep {tuple(keep.shape)}: expected ({B}, {T}) or ({B}, 1, {T})")
+    if not (0.0 <= float(sigma_min) < 1.0):
+        raise ValueError(f"infill: sigma_min {sigma_min} outside [0, 1)")
+    return x1, (keep.detach().reshape(B, T) != 0).to(torch.uint8).contiguous()
 
 
 def rows_plan(counts, solver: str = "euler") -> List[int]:
@@ -999,6 +1049,7 @@ VCONV_LOG_FIELDS = ("ef", "bm", "bn", "k1", "ntiles", "grid", "taps", "M", "cin"
 # attn_uni_vec_kernel, attn_uni_apply_kernel; grid in "grid", utterances in "B", frames per utterance in "L") and
 # FFN_LOG the fused FeedForward (k1 = 1: it adds o_b itself)
 PROJ_LOG = 0x20000
+INFILL_LOG = 0x1000000  # infill_clamp_kernel (mt_cfm_solve_infill): "B" the rows it ran on, "L" the frames per row
 UNI_LOG_PART, UNI_LOG_VEC, UNI_LOG_APPLY = 0x40000, 0x80000, 0xC0000
 FFN_LOG = 0x400000
 LOG_CONV, LOG_AUX = 1, 2

@@ -435,7 +435,7 @@ class BASECFM(nn.Module):
 
     @torch.inference_mode()
     def forward(self, mu, mask, n_timesteps, temperature=1.0, spks=None, cond=None, max_valid=None, seeds=None,
-                t_span=None):
+                t_span=None, x1=None, keep=None):
         """z = randn_like(mu)*temperature, then the Euler/midpoint loop — one HIP call. max_valid (extension, not
         in the reference signature): the most valid frames of any utterance when the caller knows it (synthesize's
         y_max); it lets the solver prove every utterance padded and use the query-independent attention.
@@ -443,11 +443,17 @@ class BASECFM(nn.Module):
         int64 [B] tensor or B ints; utterance b then starts from the seeded stream of seeds[b] (rt.seeded_noise),
         which depends on neither the batch nor the padded length, drawn inside the solve. n_timesteps (extension):
         also one count per utterance ([B] ints); t_span (extension): a time grid of n + 1 times in [0, 1] shared by
-        the batch, or one per utterance (rt.step_plan; rt.cosine_grid), instead of the reference's i / n."""
+        the batch, or one per utterance (rt.step_plan; rt.cosine_grid), instead of the reference's i / n.
+        x1, keep (extension, mel infill): x1 a normalized mel [B,80,T] and keep [B,T] (or [B,1,T]), non-zero = kept;
+        the kept valid frames follow compute_loss's y_t = (1 - (1 - sigma_min) t) z + t x1 with the utterance's own
+        noise z and come back as x1, the others are integrated as usual and see them through the estimator."""
+        rt.infill_args(x1, keep, mu.shape[0], mu.shape[1], mu.shape[2], self.sigma_min)
         rt.require_gpu(mu, mask, spks, what="CFM.forward")
         mu, mask, spks = rt.f32c(mu), rt.f32c(mask), rt.f32c(spks)
         est = self.estimator
         kw = dict(max_valid=int(max_valid or 0), t_span=t_span)
+        if x1 is not None:
+            kw.update(x1=x1, keep=keep, sigma_min=self.sigma_min)
         if seeds is not None:
             return est.engine().solve(est.packed(mu.device), None, temperature, mu, mask, spks, n_timesteps,
                                       self.solver, seeds=seeds, **kw)
@@ -531,7 +537,7 @@ class MatchaTTS(nn.Module):
 
     @torch.inference_mode()
     def synthesize(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
-                   t_span=None, token_scale=None, durations=None):
+                   t_span=None, token_scale=None, durations=None, infill_mel=None, infill_keep=None):
         """model.py:1264-1300 -> (mel [B,80,y_max], y_lengths int64 [B], attn [B,1,Tx,T_pad]).
         Extensions for mixed batches: temperature and length_scale each take a number or one value per utterance
         ([B] tensor or sequence); seeds (int64 [B] tensor or B ints) gives utterance b the noise of seeds[b], the
@@ -541,9 +547,17 @@ class MatchaTTS(nn.Module):
         Duration control: token_scale (fp32 [B,Tx] or B lists) multiplies each token's predicted length before the
         ceil; durations (integer [B,Tx] frames per token, zeros allowed) replaces the predictor, e.g. an edited
         predict_durations() or the timing align() took from a recording. durations excludes a length_scale other
-        than 1 and token_scale; a negative count raises ValueError."""
+        than 1 and token_scale; a negative count raises ValueError.
+        Mel infill: infill_mel ([B,80,Tk], denormalized, what synthesize returns) with infill_keep ([B,Tk], non-zero =
+        kept) pins those frames: they come back as given (to the rounding of normalize / denormalize) while the
+        solve fills the others around them. Frames at or past Tk are free, frames at or past y_lengths[b] ignored."""
         B, Tx = x.shape[0], x.shape[1]
         token_scale, durations = rt.duration_args(B, Tx, length_scale, token_scale, durations)
+        n_feats = self.decoder.n_feats
+        if infill_mel is not None and isinstance(infill_mel, torch.Tensor) and infill_mel.dim() == 3:
+            infill_mel, infill_keep = rt.infill_args(infill_mel, infill_keep, B, n_feats, infill_mel.shape[2])
+        elif infill_mel is not None or infill_keep is not None:
+            infill_mel, infill_keep = rt.infill_args(infill_mel, infill_keep, B, n_feats, 0)
         rt.require_gpu(x, x_lengths, spks, what="MatchaTTS.synthesize")
         rt.step_plan(n_timesteps, t_span, B)  # argument errors before any launch
         if seeds is not None:
@@ -575,8 +589,16 @@ class MatchaTTS(nn.Module):
                                  "an utterance fewer than 2^24 frames")
             t_pad = fix_len_compatibility(y_max)
             attn, mu_y, y_mask = rt.alignment(cum, y_lengths, t_pad, mu)
+            x1 = keep = None
+            if infill_mel is not None:  # normalized, then zero-padded or cropped to t_pad (frames past Tk are free)
+                tk = min(infill_mel.shape[2], t_pad)
+                x1 = torch.zeros((B, n_feats, t_pad), dtype=torch.float32, device=x.device)
+                x1[:, :, :tk] = normalize(infill_mel[:, :, :tk].to(device=x.device, dtype=torch.float32),
+                                          self.mel_mean, self.mel_std)
+                keep = torch.zeros((B, t_pad), dtype=torch.uint8, device=x.device)
+                keep[:, :tk] = infill_keep[:, :tk].to(x.device)
             z = self.decoder(mu_y, y_mask, n_timesteps, temperature, spks, cond=None, max_valid=y_max, seeds=seeds,
-                             t_span=t_span)
+                             t_span=t_span, x1=x1, keep=keep)
         finally:
             est._pk.untrust()
         mel = rt.denorm_crop(z, self.mel_mean, self.mel_std, y_max)
@@ -584,12 +606,12 @@ class MatchaTTS(nn.Module):
 
     @torch.inference_mode()
     def synthesise(self, x, x_lengths, n_timesteps, temperature=1.0, spks=None, length_scale=1.0, seeds=None,
-                   t_span=None, token_scale=None, durations=None):
+                   t_span=None, token_scale=None, durations=None, infill_mel=None, infill_keep=None):
         """Upstream-Matcha-style alias (notebooks: MOS_audiou_generator.ipynb:294) -> dict."""
         import time
         t0 = time.perf_counter()
         mel, y_lengths, attn = self.synthesize(x, x_lengths, n_timesteps, temperature, spks, length_scale, seeds,
-                                               t_span, token_scale, durations)
+                                               t_span, token_scale, durations, infill_mel, infill_keep)
         y_max = mel.shape[-1]
         dt = time.perf_counter() - t0
         return {"mel": mel, "mel_lengths": y_lengths, "attn": attn[:, :, :, :y_max],
@@ -630,3 +652,83 @@ class MatchaTTS(nn.Module):
         dur, attn, _ = rt.align(mu, mel, xl, yl, mean, std, want_attn=return_attn)
         rt.check_ids(oov)
         return (dur, attn.unsqueeze(1)) if return_attn else dur
+
+    @torch.inference_mode()
+    def edit(self, x_old, x_old_lengths, mel, mel_lengths, x_new, x_new_lengths, spans, n_timesteps, *,
+             durations_old=None, margin=0, **synthesize_kwargs):
+        """Change a few tokens of a recording and leave every other frame as it was -> (mel_new [B,80,y_max],
+        y_lengths int64 [B], keep bool [B,y_max]: the frames taken from `mel`).
+        mel [B,80,Ty] (denormalized, mel_lengths frames per row) speaks x_old; spans[b] = (a, b_old, b_new): old tokens
+        [a, b_old) are replaced by new tokens [a, b_new). The tokens before a and after the spans must be the same
+        ids and the same count in x_old and x_new (ValueError otherwise). Kept tokens keep their old durations
+        (durations_old int [B,Tx_old], or align(x_old, ..., mel, ...)), the new span gets predict_durations(x_new, ...)
+        (length_scale applies to it only). The recording's frames move to the new layout, the prefix in place and the
+        tail shifted by the span's change in frames, and are pinned there by synthesize(x_new, durations=d_new,
+        infill_mel=, infill_keep=), minus `margin` frames on each side of the span, which are generated with it.
+        synthesize_kwargs: synthesize's other arguments (temperature, spks, seeds, t_span, length_scale); durations
+        and token_scale are not accepted. Plain index operations and two host reads: not a hot path."""
+        for k in ("durations", "token_scale", "infill_mel", "infill_keep"):
+            if k in synthesize_kwargs:
+                raise ValueError(f"edit: {k} is formed here (kept tokens keep their recorded durations)")
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.shape[1] != self.decoder.n_feats:
+            raise ValueError(f"edit: mel [B,{self.decoder.n_feats},Ty] expected")
+        B = x_old.shape[0]
+        margin = int(margin)
+        if x_new.shape[0] != B or mel.shape[0] != B or len(spans) != B or margin < 0:
+            raise ValueError(f"edit: one utterance, mel and span per row of x_old ({B}) and margin >= 0 expected")
+        xo, xn = x_old.detach().cpu(), x_new.detach().cpu()
+        lo = torch.as_tensor(x_old_lengths).detach().cpu().to(torch.int64).tolist()
+        ln = torch.as_tensor(x_new_lengths).detach().cpu().to(torch.int64).tolist()
+        ml = torch.as_tensor(mel_lengths).detach().cpu().to(torch.int64)
+        if len(lo) != B or len(ln) != B or ml.shape != (B,):
+            raise ValueError("edit: one length per utterance expected")
+        Txo, Txn = x_old.shape[1], x_new.shape[1]
+        src_tok = torch.full((B, Txn), -1, dtype=torch.int64)  # the old token a new token keeps the duration of
+        for b, sp in enumerate(spans):
+            a, b_old, b_new = (int(v) for v in sp)
+            if not (0 <= a <= b_old <= lo[b] <= Txo and a <= b_new <= ln[b] <= Txn):
+                raise ValueError(f"edit: spans[{b}] = {(a, b_old, b_new)} outside the texts ({lo[b]}, {ln[b]} tokens)")
+            if lo[b] - b_old != ln[b] - b_new:
+                raise ValueError(f"edit: row {b}: {lo[b] - b_old} tokens after the old span, {ln[b] - b_new} after the "
+                                 "new one (the tails must be the same tokens)")
+            if not (torch.equal(xo[b, :a], xn[b, :a]) and torch.equal(xo[b, b_old:lo[b]], xn[b, b_new:ln[b]])):
+                raise ValueError(f"edit: row {b}: the tokens outside the spans differ between x_old and x_new")
+            src_tok[b, :a] = torch.arange(a)
+            src_tok[b, b_new:ln[b]] = torch.arange(b_old, lo[b])
+        rt.require_gpu(x_old, x_new, mel, what="MatchaTTS.edit")
+        dev = x_new.device
+        spks = synthesize_kwargs.get("spks")
+        if durations_old is None:
+            d_old = self.align(x_old, x_old_lengths, mel, mel_lengths, spks=spks)
+        else:
+            d_old = torch.as_tensor(durations_old).detach()
+            if d_old.dtype.is_floating_point or d_old.dtype == torch.bool or d_old.shape != (B, Txo):
+                raise ValueError(f"edit: durations_old: integer frame counts [{B}, {Txo}] expected")
+            d_old = d_old.to(device=dev, dtype=torch.int64)
+        d_pred = self.predict_durations(x_new, x_new_lengths, spks, synthesize_kwargs.pop("length_scale", 1.0))
+        src_tok = src_tok.to(dev)
+        d_new = torch.where(src_tok >= 0, d_old.gather(1, src_tok.clamp(min=0)), d_pred)
+        # frame layout: [0, f_a) the prefix, [f_a, g_b) the new span, [g_b, y_new) the tail = old frames [f_b, y_old)
+        a_t = torch.tensor([int(sp[0]) for sp in spans], device=dev)
+        bo_t = torch.tensor([int(sp[1]) for sp in spans], device=dev)
+        bn_t = torch.tensor([int(sp[2]) for sp in spans], device=dev)
+        zero = torch.zeros((B, 1), dtype=torch.int64, device=dev)
+        cum_o = torch.cat([zero, d_old.cumsum(1)], 1)
+        cum_n = torch.cat([zero, d_new.cumsum(1)], 1)
+        f_a = cum_o.gather(1, a_t[:, None])
+        f_b = cum_o.gather(1, bo_t[:, None])
+        g_b = cum_n.gather(1, bn_t[:, None])
+        y_old, y_new = cum_o[:, -1:], cum_n[:, -1:]
+        if not torch.equal(y_old[:, 0].cpu(), ml) or int(ml.max()) > mel.shape[2]:
+            raise ValueError(f"edit: the old durations sum to {y_old[:, 0].tolist()} frames, mel_lengths are "
+                             f"{ml.tolist()} (mel has {mel.shape[2]} frames)")
+        y_max = int(y_new.max())
+        j = torch.arange(y_max, device=dev)[None]
+        tail = (j >= g_b) & (j < y_new)
+        src = torch.where(j < f_a, j, torch.where(tail, j - (g_b - f_b), torch.full_like(j, -1)))
+        keep = (j < f_a - margin) | (tail & (j >= g_b + margin))
+        x1 = mel.to(device=dev, dtype=torch.float32).gather(
+            2, src.clamp(0, mel.shape[2] - 1)[:, None, :].expand(B, mel.shape[1], y_max))
+        mel_new, y_lengths, _ = self.synthesize(x_new, x_new_lengths, n_timesteps, durations=d_new, infill_mel=x1,
+                                                infill_keep=keep, **synthesize_kwargs)
+        return mel_new, y_lengths, keep[:, :mel_new.shape[-1]]
