@@ -16,6 +16,8 @@
  *   mt_vocoder_forward_ragged,   <- the reference pipeline's per-utterance vocoder + denoiser calls (one utterance
  *   mt_denoise_ragged               per call, mel cropped to its y_length: main.py:181-198,
  *                                   MOS_audiou_generator.ipynb:265-277) for a whole padded batch in one launch chain
+ *   mt_resample, mt_audio_stats, <- the host steps after the vocoder, main.py:198-201 (`.clamp(-1, 1)`, soundfile's
+ *   mt_audio_encode                 PCM16 write), plus rate conversion and level, which the reference leaves to callers
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
  *   mt_durations_tokens, mt_align   duration control and a forced aligner for inference: no counterpart in the
  *                                   reference (its log-prior train_standalone.py:639-644 in direct form, textbook MAS)
@@ -330,6 +332,43 @@ int mt_denoise_ragged(const float* audio, int B, int L, const int32_t* lens, int
                       float strength, float* out, void* ws, size_t ws_bytes, void* stream);
 /* |STFT| (same framing) of every frame: mag [B][1+L/256][513] (bias spectrum, denoiser.py:57-60) */
 int mt_stft_magnitude(const float* audio, int B, int L, float* mag, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Audio output stage (matcha_hip/audio_out.py is the specification on the CPU): what main.py does on
+ * the host after the vocoder (`.clamp(-1, 1)`, then soundfile), for a whole padded batch audio [B][L] fp32 whose row
+ * b is valid for its first len_b samples. Every result of row b depends on that row's valid samples alone.
+ * ------------------------------------------------------------------------------------- */
+#define MT_NORM_NONE 0
+#define MT_NORM_PEAK 1
+#define MT_NORM_RMS 2
+#define MT_ENC_F32 0
+#define MT_ENC_PCM16 1
+#define MT_ENC_MULAW 2
+/* Rational resampling by up / down (coprime, each 1 .. 1024) with a zero-phase FIR h of 2 half + 1 taps:
+ *   out[b][m] = sum_k h[half + m down - k up] audio[b][k],  m < out_lens[b] = ceil(len_b up / down) (64-bit),
+ * one fp32 FMA chain per output over the taps of its phase, in an order that depends on m alone; zero past out_lens[b]
+ * up to Lout, which is at least ceil(L up / down). len_b = lens[b] * lmul clamped to [0, L] (lens int32 [B], device;
+ * NULL: L). taps_polyphase: fp32 [up][ceil((2 half + 1) / up)], entry [p][q] = h[q up + p], zero-filled (device).
+ * out_lens int32 [B]. The table goes to LDS with the tile's input samples while both fit 64 KiB (every rate between
+ * 8 and 48 kHz from 22,050 Hz does); beyond that the kernel reads them from global memory, same bits.
+ * Workspace: mt_resample_workspace_bytes (0 and mt_last_error for a refused factor), 16-byte aligned. */
+size_t mt_resample_workspace_bytes(int half, int up, int down);
+int mt_resample(const float* audio, int B, int L, const int32_t* lens, int lmul, const float* taps_polyphase, int half,
+                int up, int down, float* out, int Lout, int32_t* out_lens, void* ws, size_t ws_bytes, void* stream);
+/* peak[b] = max |x| (fp32 [B]) and meansq[b] = sum x^2 / len_b (fp64 [B]; 0 for an empty row) over the first len_b =
+ * lens[b] samples (int32 [B], device, clamped to [0, L]; NULL: L). The squares are summed in fp64 over tiles of 4096
+ * samples counted from the row's start, then the partials in a fixed order: no atomics. */
+size_t mt_audio_stats_workspace_bytes(int B, int L);
+int mt_audio_stats(const float* audio, int B, int L, const int32_t* lens, float* peak, double* meansq, void* ws,
+                   size_t ws_bytes, void* stream);
+/* gain g_b (fp64, rounded to fp32 at the end): MT_NORM_NONE 1 (peak and meansq are not read and may be NULL);
+ * MT_NORM_PEAK level / peak[b]; MT_NORM_RMS level / sqrt(meansq[b]), with limit != 0 at most 1 / peak[b]; 1 when
+ * peak[b] == 0. level must be finite and positive. Then, in fp32, v = clamp(g_b x, -1, 1) and out[b][i] is
+ * MT_ENC_F32 v (fp32), MT_ENC_PCM16 q = rint(32767 v), half to even (int16), MT_ENC_MULAW the G.711 mu-law byte of
+ * q (uint8); past len_b (lens as in mt_audio_stats) 0, 0 and 0xFF. out: [B][L] of the encoding's type, never in
+ * place. gain_out fp32 [B], may be NULL. */
+int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const float* peak, const double* meansq,
+                    int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Log-mel featurizer (§8f rank 4), replacing train_standalone.py:164-201 `mel_spectrogram(y, 1024, 80,

@@ -23,6 +23,15 @@ int ffn_exp_flags();
 int vpair_exp_flags();
 int stft_magnitude(const float* audio, int B, int L, float* mag, hipStream_t st);
 int log_mel(const float* audio, int B, int L, const float* basis, float mean, float stdv, float* mel, hipStream_t st);
+// mt_audio.hip
+size_t resample_workspace_bytes(int half, int up, int down);
+int resample(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
+             int down, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes, hipStream_t st);
+size_t audio_stats_workspace_bytes(int B, int L);
+int audio_stats(const float* audio, int B, int L, const int* lens, float* peak, double* meansq, void* ws,
+                size_t ws_bytes, hipStream_t st);
+int audio_encode(const float* audio, int B, int L, const int* lens, const float* peak, const double* meansq,
+                 int normalize, double level, int limit, int encoding, void* out, float* gain_out, hipStream_t st);
 }  // namespace mt
 
 struct mt_encoder {
@@ -412,6 +421,24 @@ int mt_denoise_ragged(const float* audio, int B, int L, const int32_t* lens, int
                       float strength, float* out, void* ws, size_t ws_bytes, void* stream) {
   MT_REQUIRE(audio && lens && bias_spec && out, "denoise_ragged: null argument");
   return mt::denoise(audio, B, L, bias_spec, strength, out, ws, ws_bytes, (hipStream_t)stream, lens, lmul);
+}
+
+// ---- audio output stage ----
+size_t mt_resample_workspace_bytes(int half, int up, int down) { return mt::resample_workspace_bytes(half, up, down); }
+int mt_resample(const float* audio, int B, int L, const int32_t* lens, int lmul, const float* taps_polyphase, int half,
+                int up, int down, float* out, int Lout, int32_t* out_lens, void* ws, size_t ws_bytes, void* stream) {
+  return mt::resample(audio, B, L, lens, lmul, taps_polyphase, half, up, down, out, Lout, out_lens, ws, ws_bytes,
+                      (hipStream_t)stream);
+}
+size_t mt_audio_stats_workspace_bytes(int B, int L) { return mt::audio_stats_workspace_bytes(B, L); }
+int mt_audio_stats(const float* audio, int B, int L, const int32_t* lens, float* peak, double* meansq, void* ws,
+                   size_t ws_bytes, void* stream) {
+  return mt::audio_stats(audio, B, L, lens, peak, meansq, ws, ws_bytes, (hipStream_t)stream);
+}
+int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const float* peak, const double* meansq,
+                    int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream) {
+  return mt::audio_encode(audio, B, L, lens, peak, meansq, normalize, level, limit, encoding, out, gain_out,
+                          (hipStream_t)stream);
 }
 
 size_t mt_maximum_path_workspace_bytes(int B, int Tx, int Ty) { return mt::mas_workspace_bytes(B, Tx, Ty); }

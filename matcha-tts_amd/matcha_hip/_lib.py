@@ -92,6 +92,11 @@ SIGNATURES = {
     "mt_denoise_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mt_denoise": (c_int, [P, c_int, c_int, P, c_float, P, P, c_size_t, P]),
     "mt_denoise_ragged": (c_int, [P, c_int, c_int, P, c_int, P, c_float, P, P, c_size_t, P]),
+    "mt_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mt_resample": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "mt_audio_stats_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mt_audio_stats": (c_int, [P, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "mt_audio_encode": (c_int, [P, c_int, c_int, P, P, P, c_int, c_double, c_int, c_int, P, P, P]),
     "mt_maximum_path_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mt_decoder_step_times_workspace_bytes": (c_size_t, [P, c_int, c_int]),
     "mt_decoder_step_times": (c_int, [P, P, P, P, P, P, P, c_int, c_int, P, P, c_size_t, P]),

@@ -832,6 +832,121 @@ def denoise(audio: torch.Tensor, bias_spec: torch.Tensor, strength: float, lengt
     return out
 
 
+# ---- audio output stage (audio_out.py is the specification) ------------------------------------
+
+# outputs per workgroup of resample_kernel (mt_audio.hip RS_TN): tests put utterance ends around its multiples
+RESAMPLE_TILE = 2048
+NORMALIZE_CODES = {None: 0, "peak": 1, "rms": 2}
+ENCODING_CODES = {"f32": (0, torch.float32), "pcm16": (1, torch.int16), "mulaw": (2, torch.uint8)}
+DEFAULT_LEVEL = {None: 1.0, "peak": 0.95, "rms": 10 ** (-20 / 20)}  # 0.95: hifigan/meldataset.py's normalisation
+
+
+class ResamplePlan:
+    """One rate change: the factor, the filter (h fp64 on the host, specification) and its fp32 taps by phase
+    [up][ceil((2 half + 1) / up)] on the device, as mt_resample reads them."""
+
+    def __init__(self, src: int, dst: int, zeros: int, beta: float, device: torch.device):
+        from . import audio_out
+        self.src, self.dst = int(src), int(dst)
+        self.up, self.down = audio_out.rates(src, dst)
+        self.h, self.half = audio_out.design_filter(self.up, self.down, zeros, beta)
+        self.taps_host = audio_out.polyphase(self.h, self.half, self.up).astype("float32")
+        self.taps = torch.from_numpy(self.taps_host).to(device)
+        self.device = device
+
+    def out_length(self, n: int) -> int:
+        return -((-int(n) * self.up) // self.down)
+
+
+_PLANS: Dict[tuple, ResamplePlan] = {}
+
+
+def resample_plan(src: int, dst: int, zeros: int = 10, beta: float = 5.0, device=None) -> ResamplePlan:
+    """The plan of src -> dst Hz, cached per (src, dst, zeros, beta, device). ValueError for a factor above 1024."""
+    from . import audio_out
+    audio_out.rates(src, dst)  # refuse the factor before anything touches the device
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise HipPathError(f"resample_plan: the output stage runs on the MI355X (ROCm) device only; got {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(src), int(dst), int(zeros), float(beta), device.index)
+    plan = _PLANS.get(key)
+    if plan is None:
+        plan = _PLANS[key] = ResamplePlan(src, dst, zeros, beta, device)
+    return plan
+
+
+def _lens32(lengths, B: int, device) -> Optional[torch.Tensor]:
+    if lengths is None:
+        return None
+    lens = torch.as_tensor(lengths).to(device=device, dtype=torch.int32).contiguous()
+    if lens.shape != (B,):
+        raise ValueError(f"lengths {tuple(lens.shape)}: expected ({B},)")
+    return lens
+
+
+def resample(audio: torch.Tensor, plan: ResamplePlan, lengths=None, lmul: int = 1):
+    """audio [B, L] -> (out fp32 [B, ceil(L up / down)], out_lens int32 [B]). lengths (int [B] in units of `lmul`
+    samples, or None = L): row b is resampled as an utterance of that length alone, ceil(len up / down) samples,
+    zero after them (mt_resample)."""
+    require_gpu(audio, what="resample")
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    Lout = plan.out_length(L)
+    out = torch.empty((B, Lout), dtype=torch.float32, device=audio.device)
+    out_lens = torch.empty((B,), dtype=torch.int32, device=audio.device)
+    L_ = lib()
+    taps = plan.taps if plan.taps.device == audio.device else plan.taps.to(audio.device)
+    ws = _Workspace.get(L_.mt_resample_workspace_bytes(plan.half, plan.up, plan.down), audio.device)
+    check(L_.mt_resample(ptr(audio), B, L, ptr(lens), int(lmul), ptr(taps), plan.half, plan.up, plan.down, ptr(out),
+                         Lout, ptr(out_lens), ws.data_ptr(), ws.numel(), stream_handle(audio.device)), "resample")
+    return out, out_lens
+
+
+def audio_stats(audio: torch.Tensor, lengths=None):
+    """audio [B, L], lengths in samples (int [B], or None = L) -> (peak fp32 [B] = max |x|, meansq fp64 [B] = mean
+    x^2) over each row's valid samples (mt_audio_stats)"""
+    require_gpu(audio, what="audio_stats")
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    peak = torch.empty((B,), dtype=torch.float32, device=audio.device)
+    meansq = torch.empty((B,), dtype=torch.float64, device=audio.device)
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_audio_stats_workspace_bytes(B, L), audio.device)
+    check(L_.mt_audio_stats(ptr(audio), B, L, ptr(lens), ptr(peak), ptr(meansq), ws.data_ptr(), ws.numel(),
+                            stream_handle(audio.device)), "audio_stats")
+    return peak, meansq
+
+
+def encode_audio(audio: torch.Tensor, lengths=None, normalize=None, level=None, limit: bool = True,
+                 encoding: str = "f32", stats=None):
+    """audio [B, L], lengths in samples -> (out [B, L] fp32 / int16 / uint8, gain fp32 [B]): each row times its gain
+    (audio_out.gain_ref of its peak and mean square: `stats`, or audio_stats of it), clamped to [-1, 1], encoded
+    (mt_audio_encode); past a row's length 0, 0 and 0xFF."""
+    require_gpu(audio, what="encode_audio")
+    if normalize not in NORMALIZE_CODES:
+        raise ValueError(f"normalize must be one of {list(NORMALIZE_CODES)}, got {normalize!r}")
+    if encoding not in ENCODING_CODES:
+        raise ValueError(f"encoding must be one of {list(ENCODING_CODES)}, got {encoding!r}")
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    peak = meansq = None
+    if normalize is not None:
+        peak, meansq = audio_stats(audio, lens) if stats is None else stats
+    code, dtype = ENCODING_CODES[encoding]
+    out = torch.empty((B, L), dtype=dtype, device=audio.device)
+    gain = torch.empty((B,), dtype=torch.float32, device=audio.device)
+    level = DEFAULT_LEVEL[normalize] if level is None else float(level)
+    check(lib().mt_audio_encode(ptr(audio), B, L, ptr(lens), ptr(peak), ptr(meansq), NORMALIZE_CODES[normalize],
+                                level, int(bool(limit)), code, ptr(out), ptr(gain), stream_handle(audio.device)),
+          "audio_encode")
+    return out, gain
+
+
 def maximum_path(neg_cent: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """train_standalone.py:280-325 on the GPU: neg_cent [B,Tx,Ty], attention mask [B,Tx,Ty] (x_mask x
     y_mask) -> one-hot monotonic path [B,Tx,Ty] in neg_cent's dtype. The lengths are the mask's row /
