@@ -48,26 +48,6 @@ constexpr int FLDS = TAB_OFF + 4 * FE * 4;
 static_assert(FLDS <= 160 * 1024, "LDS budget");
 }  // namespace
 
-__device__ __forceinline__ void ff_glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-__device__ __forceinline__ void ff_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void ff_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ff_for<I + 1, N>(f);
-  }
-}
-
 template <bool MASK, bool OVL, bool UNI, bool PFB = false, int SP = ST_PLAIN>  // SP: the output store's policy (mt_common.h)
 __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
   __shared__ __attribute__((aligned(1024))) char smem[FLDS];
@@ -125,7 +105,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
     for (int i = 0; i < 2; ++i) {
       int wo = woff[i];
       asm volatile("" : "+v"(wo));
-      ff_glds16(base + wo, smem + so + i * 1024);
+      glds16(base + wo, smem + so + i * 1024);
     }
   };
   const char* xg = reinterpret_cast<const char*>(a.x);
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
       const int q = lp ^ (r & 6);
       const int f = n0 + r;
       const char* src = f < NF ? xg + ((size_t)f * FC + kc * 64) * 2 + q * 16 : zg + q * 16;
-      ff_glds16(src, smem + xo + kc * FCHUNK + (p & 15) * 1024);
+      glds16(src, smem + xo + kc * FCHUNK + (p & 15) * 1024);
     }
   };
   // per-frame operands of a tile (this lane's 2 frames): LayerNorm partials, mask
@@ -211,11 +191,6 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
     }
   };
   using NV0 = std::integral_constant<int, 0>;
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
   float2 lns[2];
   // FF1 epilogue of chunk j, fragment group (fp, fn): mt_vconv's VE_LN | VE_LNP | VE_SNAKE packed epilogue -> 16 bytes
   // of h_j (bf16) per lane in the LDS row layout (8 consecutive channels)
@@ -305,7 +280,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
         for (int o = 1; o < 8; o <<= 1) q2 += __shfl_xor(q2, o, 64);
         if (q == 0) *reinterpret_cast<float2*>(st + 8 * r + 2 * slab) = float2{mu, q2};
       }
-      ff_barrier();
+      lds_barrier();
 #pragma unroll
       for (int fn = 0; fn < 2; ++fn) {
         const int r = wn * 32 + fn * 16 + l16;
@@ -391,14 +366,14 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
     constexpr int EG = decltype(EGc)::value;
     __builtin_amdgcn_sched_barrier(0);
     vc_wait_vmcnt<0>();
-    ff_barrier();
+    lds_barrier();
     if constexpr (FI) tile_start(cur_n0);
     issue_w(j2, U2, slot2);
     if constexpr (HW) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) h_store(g >> 1, g & 1, hreg[g]);
     }
-    if constexpr (XB) ff_barrier();
+    if constexpr (XB) lds_barrier();
     constexpr int boff = U < 4 ? XR_OFF + U * FCHUNK : H_OFF + ((U - 4) >> 1) * FCHUNK;
     if constexpr (R0) read_frag(F0, 0, slot, boff);
     read_frag(F1, 1, slot, boff);
@@ -436,7 +411,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
       // P: FF1(0), steps 0..3; weights of steps 2, 3 (P) then 4, 5 (block 0: FF1(1) x chunks 0, 1)
       {
         const int q = qsr;
-        ff_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
+        vc_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value;
           using U2 = std::integral_constant<int, (r + 2 < 4 ? r + 2 : r - 2)>;
           using U1 = std::integral_constant<int, (r + 1 < 4 ? r + 1 : 0)>;
@@ -453,7 +428,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
       // blocks b = 0..6: FF1(b+1) x chunks 0..3, then FF2(b) (h chunk 0 halves 0, 1, h chunk 1 halves 0, 1)
       for (int b = 0; b < 7; ++b) {
         const int q = qsr;
-        ff_for<0, 8>([&](auto rc) __attribute__((always_inline)) {
+        vc_for<0, 8>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value;
           const int j = r < 4 ? b + 1 : b;
           // the weights of step s + 2: this block's step r + 2, or the next block's (or E's) first two
@@ -487,7 +462,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
       // steps 2, 3, then the next tile's P steps 0, 1
       {
         const int q = qsr;
-        ff_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
+        vc_for<0, 4>([&](auto rc) __attribute__((always_inline)) {
           constexpr int r = decltype(rc)::value;
           using U = std::integral_constant<int, 4 + r>;
           using U2 = std::integral_constant<int, (r + 2 < 4 ? 4 + r + 2 : r - 2)>;
@@ -502,7 +477,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
       __builtin_amdgcn_sched_barrier(0);
       ff2_epilogue(n0);
       if (ti + 1 < nmine) {
-        ff_barrier();
+        lds_barrier();
         const int n1 = (t0 + (ti + 1) * gx) * FBN;
         frame_loads(n1);
         issue_x(n1);
@@ -532,7 +507,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
 #pragma unroll
         for (int fn = 0; fn < 2; ++fn) acc2[ch][fm][fn] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < 8; ++j) {
-      ff_for<0, 8>([&](auto uc) __attribute__((always_inline)) {
+      vc_for<0, 8>([&](auto uc) __attribute__((always_inline)) {
         constexpr int u = decltype(uc)::value;
         auto sel = [&](int k) {  // (qs + k) % 3
           const int v = qs + k;
@@ -548,7 +523,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
         } else {
           vc_wait_vmcnt<0>();
         }
-        ff_barrier();
+        lds_barrier();
         if (u == 0 && j == 0) tile_start(n0);
         // weights of step s + 2 into the slot of step s - 1 (every wave's reads of it ended before this barrier)
         if constexpr (u + 2 < 8) issue_w(j, u + 2, slot2);
@@ -589,7 +564,7 @@ __global__ __launch_bounds__(FNT) void ffn_kernel(FfnArgs a) {
     ff2_epilogue(n0);
     // the next tile's rows replace this one's: every wave's residual reads of them are done after this barrier
     if (ti + 1 < nmine) {
-      ff_barrier();
+      lds_barrier();
       const int n1 = (t0 + (ti + 1) * gx) * FBN;
       frame_loads(n1);
       issue_x(n1);
@@ -607,16 +582,6 @@ int ffn_knob() {
     g_ffn = e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : 3;
   }
   return g_ffn;
-}
-int ffn_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
 }
 }  // namespace
 
@@ -657,7 +622,7 @@ int launch_ffn(const FfnArgs& a, hipStream_t st) {
                  a.frames > 0,
              "ffn: null argument / empty");
   const int ntiles = (a.frames + FBN - 1) / FBN;
-  const int G = std::min(ntiles, ffn_cus());
+  const int G = std::min(ntiles, cu_count());
   MT_REQUIRE(!a.ovec || a.T > 0, "ffn: ovec needs T");
   const int mode = ffn_knob();  // 1 serial, 2 overlapped FF1 epilogues, 3 serial with frame-only prefetch
   void (*kern)(FfnArgs);

@@ -95,27 +95,6 @@ constexpr int rb_nst() {  // the epilogue's stores per wave and tile
 
 }  // namespace
 
-__device__ __forceinline__ void rb_glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void rb_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// compile-time loop: f(integral_constant<int, I>) for I in [0, N)
-template <int I, int N, class F>
-__device__ __forceinline__ void rb_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    rb_for<I + 1, N>(f);
-  }
-}
-
 template <int EF, int C, int K, int LW, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
   static_assert(SP == ST_PLAIN || (RB_BUF & 4) != 0, "the store policy rides on the buffer stores");
@@ -212,7 +191,7 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
       for (int i = 0; i < WPW; ++i) {
         int wo = woff[i];
         asm volatile("" : "+v"(wo));  // per-step address (see read_frag)
-        rb_glds16(base + wo, smem + so + i * 1024);
+        glds16(base + wo, smem + so + i * 1024);
       }
     }
   };
@@ -250,7 +229,7 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
         const int f = f0 + r;
         const bool ok = r < R && f >= 0 && f < Lx;
         const char* src = ok ? xb + (size_t)f * C * 2 + q * 16 : reinterpret_cast<const char*>(a.zero) + q * 16;
-        rb_glds16(src, dst + j * 1024);
+        glds16(src, dst + j * 1024);
       }
     }
   };
@@ -258,6 +237,8 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
   f32x4 acc[4][RFN];  // a tile's first K-slice starts from the MFMA's zero C operand (no zeroing pass)
 
   const int g4 = lane >> 4, l16 = lane & 15;
+  // mt_pipe.h's swap16, kept as a local (captured by the lambdas below): calling the shared function instead moves
+  // this kernel's register allocation (+4 VGPRs in rbconv_kernel<17, 128, 11, 4>)
   auto swap16 = [](uint32_t& x, uint32_t& y) {
     const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
     x = r[0];
@@ -315,10 +296,8 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
           const uint32_t yy[2] = {h ? yy0 : yx0, h ? yy1 : yx1};
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            f32x2 v = f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]} + f32x2{bias4[2 * u], bias4[2 * u + 1]};
-            if constexpr ((EF & VE_RESID) != 0) v = v + unpk_bf16(rr[u]);
-            if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-            if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
+            const f32x2 v = res_sum<EF>(f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]},
+                                        f32x2{bias4[2 * u], bias4[2 * u + 1]}, rr[u], yy[u], a.div);
             const uint32_t rb = pk_bf16(v);
             uint32_t av = 0u;
             if constexpr (RB_LMAX) av = (EF & VE_ACT) ? lrelu_pk_f(v, a.slope) : (EF & VE_DUAL) ? lrelu_pk(rb, a.slope) : 0u;
@@ -435,10 +414,10 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
     if constexpr (ACTIN) vc_wait_vmcnt<0>();  // chunk 0's rows too (RL = 2: no step before step 0 publishes them)
     else vc_wait_vmcnt<SCH::wait_first(-1)>();
   }
-  rb_barrier();
+  step_barrier();
   if constexpr (ACTIN) {
     act_pass(0);
-    rb_barrier();
+    step_barrier();
   }
   Frag F0, F1;
   read_frag(F0, 0, 0, 0, 0);
@@ -448,7 +427,7 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
   // constant when S % 4 == 0 (C = 256), else (C = 128, S = 2K = 2 mod 4) the tile's parity adds 2 ----
   for (int ti = 0; ti < nmine; ++ti) {
     const int sb = (S % RNW == 0) ? 0 : (ti & 1) * 2;  // slot base of this tile
-    rb_for<0, S>([&](auto uc) {
+    vc_for<0, S>([&](auto uc) {
       constexpr int s = decltype(uc)::value;           // step in the tile
       constexpr int c = s / K, t = s % K;              // chunk, tap
       constexpr int xbuf = c % 2;
@@ -473,7 +452,7 @@ __global__ __launch_bounds__(RNT) void rbconv_kernel(VConvArgs a) {
       // writes LDS that other waves read after it
       if constexpr (ACTIN && t == K - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       VP_TS(0);
-      if constexpr ((RB_EXP & 8) == 0) rb_barrier();
+      if constexpr ((RB_EXP & 8) == 0) step_barrier();
       VP_TS(1);
       // the epilogue's residual / old-xs loads, RB_EPI_AT steps before the tile's last (compiler-visible loads: the
       // epilogue's use waits for them, the counted waits leave them out)

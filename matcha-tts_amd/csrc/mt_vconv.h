@@ -4,9 +4,7 @@
 // lrelu(x) next to x), so every operand byte goes global -> LDS by `global_load_lds_dwordx4` with no
 // VGPR round trip and no prologue transform (see mt_vconv.hip for the pipeline).
 #pragma once
-#include <type_traits>
-
-#include "mt_common.h"
+#include "mt_pipe.h"
 
 namespace mt {
 
@@ -48,6 +46,27 @@ enum : int {
                      // per tile from the producer's VE_GNSTATS partials (ResnetBlock1D block2 -> + res(x),
                      // model.py:777-790; replaces a separate gn_apply pass)
 };
+
+// THE ResBlock output arithmetic, two channels of one packed word: acc + bias [+ resid] [old xs +] [/ div] in this
+// operand order and with this reciprocal. The per-layer kernels (mt_vconv's packed epilogue, mt_rbconv) and the fused
+// pair kernels (mt_vpair.h) must produce the same bits, and -ffp-contract fuses differently per code shape
+// (mt_common.h), so every kernel of the family calls this one definition; none spells the sum out itself.
+template <int EF>
+__device__ __forceinline__ f32x2 res_sum(f32x2 acc, f32x2 bias, uint32_t resid, uint32_t xs, float div) {
+  f32x2 v = acc + bias;
+  if constexpr ((EF & VE_RESID) != 0) v = v + unpk_bf16(resid);
+  if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(xs) + v;
+  if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, div, 1.f / div), div_rn(v.y, div, 1.f / div)};
+  return v;
+}
+// ... rounded to the stored chain state o1, and o2 = its activated copy lrelu(o1) as max(x, slope x) (for files built
+// with IEEE mode off: the pair kernels)
+template <int EF>
+__device__ __forceinline__ void res_out(f32x2 acc, f32x2 bias, uint32_t resid, uint32_t xs, float div, float slope,
+                                        uint32_t& o1, uint32_t& o2) {
+  o1 = pk_bf16(res_sum<EF>(acc, bias, resid, xs, div));
+  o2 = lrelu_pk(o1, slope);
+}
 
 // Compile-time K-loop schedule (mt_vconv CTN / CTT kernels and mt_rbconv). RL: the rows of a chunk are published
 // RL steps before its first step (1; 2 for mt_rbconv's VE_ACTIN, whose in-LDS pass over them runs in between). Per
@@ -137,15 +156,6 @@ struct SchedReg {
 template <int FAM, int NCH, int TAPS, int NW, int NXB, int TX, int WPW, int XPW, int NST, int RL, int PW>
 const int SchedReg<FAM, NCH, TAPS, NW, NXB, TX, WPW, XPW, NST, RL, PW>::reg =
     sched_register({FAM, NCH, TAPS, NW, NXB, TX, WPW, XPW, NST, RL, PW}, &SchedReg::waits);
-
-// compile-time loop: f(integral_constant<int, I>) for I in [I0, N)
-template <int I, int N, class F>
-__device__ __forceinline__ void vc_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    vc_for<I + 1, N>(f);
-  }
-}
 
 template <int N>
 __device__ __forceinline__ void vc_wait_vmcnt() {

@@ -73,40 +73,18 @@ struct VT {
 };
 }  // namespace
 
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// s_waitcnt vmcnt(k) for a wave-uniform runtime bound n, with k the largest of {0,2,4,7,10,15,23,31} <= n:
-// waiting for fewer outstanding operations than allowed is always correct (only stricter), and a
-// three-level branch tree keeps the scalar cost per step small (a 64-way switch was ~40 SALU + branches)
-__device__ __forceinline__ void wait_vmcnt(int n) {
+// the runtime-cursor loops' wait and step barrier (mt_pipe.h), which the timing experiments drop
+__device__ __forceinline__ void vc_wait(int n) {
 #if defined(VCONV_EXP) && VCONV_EXP == 1  // timing experiment only: no DMA waits (wrong results)
   return;
 #endif
-  if (n < 7) {
-    if (n < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (n < 4) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else if (n < 15) {
-    if (n < 10) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  } else {
-    if (n < 23) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    else if (n < 31) asm volatile("s_waitcnt vmcnt(23)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-  }
+  wait_vmcnt(n);
 }
-
 __device__ __forceinline__ void raw_barrier() {
 #if defined(VCONV_EXP) && VCONV_EXP == 2  // timing experiment only: no step barrier (wrong results)
   return;
 #endif
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
+  step_barrier();
 }
 
 #ifndef VC_CT_LOADERS
@@ -308,16 +286,7 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int g4 = lane >> 4, l16 = lane & 15;
-  // Epilogue I/O is 16 bytes per lane: blocks X = (fm, fn) and Y = (fm + 1, fn) hold, per lane, 4
-  // channels of one frame each; v_permlane16_swap (odd 16-lane rows of X <-> even rows of Y) turns
-  // them into 8 consecutive channels per lane (row g4: X or Y by g4 & 1, channels +8 by g4 >> 1), so a
-  // wave moves 64 B contiguous per frame per instruction. The swap is an involution, so loaded
-  // residuals are swapped back into the accumulator layout the same way.
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
+  // Epilogue I/O is 16 bytes per lane (swap16, mt_pipe.h), so a wave moves 64 B contiguous per frame per instruction
   const int ch16 = wm * 64 + (g4 & 1) * 16 + (g4 >> 1) * 8;  // + fm * 16 (fm even): this lane's 8 channels
   // residual / accumulator values of the tile, 16 B per lane: loaded at the start of the tile's last
   // step, consumed after its MFMAs
@@ -545,10 +514,8 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
             // the HiFi-GAN / plain epilogues as packed fp32 pairs (same operations and order as the scalar path)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-              f32x2 v = f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]} + f32x2{bias4[2 * u], bias4[2 * u + 1]};
-              if constexpr ((EF & VE_RESID) != 0) v = v + unpk_bf16(rr[u]);
-              if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-              if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
+              f32x2 v = res_sum<EF>(f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]},
+                                    f32x2{bias4[2 * u], bias4[2 * u + 1]}, rr[u], yy[u], a.div);
               if constexpr ((EF & VE_MASK) != 0) v = v * mk[fn];
               if constexpr ((EF & VE_PMASK) != 0) v = v * pmk;
               const uint32_t rb = pk_bf16(v);
@@ -940,7 +907,7 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
   int mW[NWSLOT - 2];  // `issued` after the weights of steps qq+1 .. qq+NWSLOT-2
 #pragma unroll
   for (int i = 0; i < NWSLOT - 2; ++i) mW[i] = stage_w();
-  wait_vmcnt(issued - max(m0w, pop_x()));
+  vc_wait(issued - max(m0w, pop_x()));
   raw_barrier();
 #if defined(VCONV_TS)
   ts_v[1] = __builtin_amdgcn_s_memrealtime();
@@ -958,7 +925,7 @@ __global__ __launch_bounds__(NT) void vconv_kernel(VConvArgs a) {
     }
     // publish step qq+1's weights (and rows, on a chunk's first tap); every wave's reads of step qq-1
     // are done (lgkmcnt), so its weight slot and, on a chunk change, the old row buffer may be restaged
-    if (qq + 1 < Q) wait_vmcnt(issued - (rt == 0 ? max(mW[0], pop_x()) : mW[0]));
+    if (qq + 1 < Q) vc_wait(issued - (rt == 0 ? max(mW[0], pop_x()) : mW[0]));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     raw_barrier();
     const bool tile_end = t == taps - 1 && c == nch - 1;
@@ -1164,16 +1131,6 @@ static int xcd_tiles_knob() {
 }
 
 int xcd_remap_enabled() { return xcd_tiles_knob(); }
-
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
 
 __global__ void vconv_wsum_kernel(const bf16* __restrict__ img, int nk, int Mpad, int cout, float* __restrict__ out) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;

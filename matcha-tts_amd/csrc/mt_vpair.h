@@ -2,6 +2,9 @@
 // stages, bf16: the intermediate stays in LDS and the input's activation is applied on chip (mt_vpair128.hip,
 // mt_vpair.hip, mt_vpair32.hip).
 #pragma once
+#include <algorithm>
+
+#include "mt_probe.h"
 #include "mt_ragged.h"
 #include "mt_vconv.h"
 
@@ -147,6 +150,115 @@ struct VpkReg {
 template <int FAM, class SCH, int EF>
 const int VpkReg<FAM, SCH, EF>::reg =
     sched_register({FAM, SCH::NS, SCH::NXP, SCH::XSP, SCH::NACC, SCH::NST, SCH::NWS, EF, 0, 0, 0}, &VpkReg::waits);
+
+// ---- what the pair kernels share (vpair_kernel, vpair3_kernel, vpair128_kernel, vpair32_kernel) ----
+
+// A persistent workgroup's walk over the launch's tiles of BN output frames: the ragged tile map built in LDS
+// (mt_ragged.h; null lens: every utterance has L frames), the tile count read as a scalar, and workgroup g of G taking
+// tiles gl, gl + G, ... with gl the XCD-major remap of g (G % 8 == 0: each XCD, which the dispatcher fills round-robin,
+// walks a contiguous range of tiles). init() is called by every thread and returns false when the workgroup has no tile.
+struct PairWalk {
+  const int *rtc, *rlv;
+  bool rag;
+  int B, L, BN, ntn, G, gl, nmine;
+  RagWalk walk;
+  __device__ __forceinline__ bool init(const VPairArgs& a, char* rag_lds, int bn, int tid) {
+    B = a.B, L = a.L, BN = bn;
+    ntn = (L + BN - 1) / BN;
+    rag = a.lens != nullptr;
+    int* tc = reinterpret_cast<int*>(rag_lds);
+    rtc = tc, rlv = tc + RAG_MAXB;
+    if (rag) {
+      rag_build(tc, tc + RAG_MAXB, a.lens, a.lmul, L, 0, L, B, BN, tid);
+      __syncthreads();
+    }
+    const int ntiles = __builtin_amdgcn_readfirstlane(rag ? rtc[B - 1] : B * ntn);  // scalar: so is the tile walk
+    const int g = blockIdx.x;
+    G = gridDim.x;
+    gl = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
+    nmine = gl < ntiles ? (ntiles - gl + G - 1) / G : 0;
+    return nmine != 0;
+  }
+  __device__ __forceinline__ RagTile at(int ti) {  // (utterance, first frame, valid frames) of this workgroup's tile ti
+    const int tile = __builtin_amdgcn_readfirstlane(gl + ti * G);
+    if (rag) return walk.at(rtc, rlv, B, BN, tile);
+    RagTile t;
+    t.b = tile / ntn;
+    t.n0 = (tile - t.b * ntn) * BN;
+    t.lv = L;
+    return t;
+  }
+};
+
+// the pair's biases as an fp32 table [b1 | b2] of 2 C floats in LDS, published to the workgroup
+template <int C, int NT>
+__device__ __forceinline__ void pair_load_bias(float* par, const VPairArgs& a, int tid) {
+  for (int i = tid; i < C; i += NT) {
+    par[i] = a.b1[i];
+    par[C + i] = a.b2[i];
+  }
+  __syncthreads();
+}
+
+// ---- host side: what launch_vpair / launch_vpair128 / launch_vpair32 share ----
+
+// the argument checks (name: the error strings' prefix; supported: the kernel's own k / d test)
+inline int pair_check(const char* name, int ef, const VPairArgs& a, bool supported) {
+  MT_REQUIRE(!(ef & VE_DIV) || div_rn_ok(a.div), "%s: VE_DIV divisor %g outside the exactly-checked set (div_rn)", name,
+             (double)a.div);
+  MT_REQUIRE(a.x && a.w1 && a.w2 && a.b1 && a.b2 && a.y && a.zero && a.trash && a.B > 0 && a.L > 0,
+             "%s: null argument / empty", name);
+  MT_REQUIRE(supported, "%s: k %d d %d", name, a.taps, a.dil);
+  MT_REQUIRE(!(ef & VE_DUAL) || a.y2, "%s: y2", name);
+  MT_REQUIRE(a.y != a.x, "%s: y must not alias x (neighbour tiles read x's halo)", name);
+  return 0;
+}
+
+// The runtime epilogue ef as a compile-time constant: f(integral_constant<int, E>) for the pair epilogues, OPT the
+// optional ones the calling kernel compiles in (VE_Y2ONLY, VE_POST). -> false: ef is not compiled in.
+template <int OPT = 0, class F>
+bool pair_with_ef(int ef, F&& f) {
+#define MT_PAIR_EF(E) \
+  case (E): f(std::integral_constant<int, (E)>{}); return true
+  switch (ef) {
+    MT_PAIR_EF(0);
+    MT_PAIR_EF(VE_ACCUM);
+    MT_PAIR_EF(VE_ACCUM | VE_DIV);
+    MT_PAIR_EF(VE_ACCUM | VE_DIV | VE_DUAL);
+    MT_PAIR_EF(VE_DIV);
+    MT_PAIR_EF(VE_DIV | VE_DUAL);
+    case VE_ACCUM | VE_DIV | VE_DUAL | VE_Y2ONLY:
+      if constexpr ((OPT & VE_Y2ONLY) != 0) f(std::integral_constant<int, VE_ACCUM | VE_DIV | VE_DUAL | VE_Y2ONLY>{});
+      return (OPT & VE_Y2ONLY) != 0;
+    case VE_ACCUM | VE_DIV | VE_POST:
+      if constexpr ((OPT & VE_POST) != 0) f(std::integral_constant<int, VE_ACCUM | VE_DIV | VE_POST>{});
+      return (OPT & VE_POST) != 0;
+  }
+#undef MT_PAIR_EF
+  return false;
+}
+
+// One pair launch around the kernel's own choice of instantiation: tiles of bn output frames, at most one workgroup
+// per CU, the probe (the pair is two of the family's convs: SURVEY §8d algorithmic FLOPs and layer-boundary bytes) and
+// the launch log's record. launch(G) starts the kernel on G workgroups; false: ef is not compiled in.
+template <class F>
+int pair_launch(const char* name, int C, int bn, int ef, const VPairArgs& a, hipStream_t st, int tag, F&& launch) {
+  const long ntiles = (long)a.B * ((a.L + bn - 1) / bn);
+  MT_REQUIRE(ntiles < (1L << 31), "%s: too many tiles", name);
+  const int G = (int)std::min<long>(ntiles, cu_count());
+  const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
+  const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
+  probe_begin(PROBE_VCONV, st);
+  if (!launch(G)) {
+    set_error("%s: epilogue %d not compiled in", name, ef);
+    return -1;
+  }
+  MT_CHECK_HIP(hipGetLastError());
+  probe_end(PROBE_VCONV, st, flops, bytes, tag);
+  const int rec[VCLOG_FIELDS] = {ef | 0x10000, C, bn, 0, (int)ntiles, G, a.taps, C, C, a.B, a.L};
+  vclog_record(rec);
+  return 0;
+}
 
 // Round-5 pair-kernel variants, each bit-identical to the kernel it replaces (mt_vpair_set_kernels): bit 0 the
 // 64-channel compile-time-K ring kernel (vpair_kernel<EF, 7 | 11>), bit 1 the 128-channel one (vpair128_kernel<EF, 3>).

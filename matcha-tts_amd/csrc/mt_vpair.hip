@@ -66,45 +66,6 @@ static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 template <int EF, int K>
 using VpSched = VpkSched<EF, (K > 0 ? (K + 1) / 2 : 2), XROWS / 64, FN, (K > 0 ? (K + 1) / 2 : 2), NWS>;
 
-__device__ __forceinline__ void vp_glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-__device__ __forceinline__ void vp_wait_vmcnt(int n) {
-  if (n < 7) {
-    if (n < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (n < 4) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else if (n < 15) {
-    if (n < 10) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  } else {
-    if (n < 23) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    else if (n < 31) asm volatile("s_waitcnt vmcnt(23)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-  }
-}
-
-__device__ __forceinline__ void vp_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-// a K-loop step's barrier: publishes LDS-DMA data (each wave waited for its own with vmcnt) and frees the ring slot
-// of two steps back. No LDS write is in flight there, and the reads still in flight (the next step's first K-slice)
-// touch neither the slot the step's DMA overwrites nor anything another wave writes, so no lgkmcnt drain: the
-// compiler waits for them where the MFMAs use them
-__device__ __forceinline__ void vp_step_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-
 template <int EF, int K = 0, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
 __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
   static_assert(SP == ST_PLAIN || VP_BUF, "the store policy rides on the buffer stores");
@@ -114,40 +75,15 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
   const int g4 = lane >> 4, l16 = lane & 15, lrow = lane >> 3, lp = lane & 7;
   const int k = K > 0 ? K : a.taps, d = a.dil, L = a.L;
   const int h1 = d * (k - 1) / 2, h2 = (k - 1) / 2;
-  const int ntn = (L + BN - 1) / BN;
-  // ragged batch: the live tiles of each utterance (mt_ragged.h)
-  const bool rag = a.lens != nullptr;
-  int* rtc = reinterpret_cast<int*>(smem + RAG_OFF);
-  int* rlv = rtc + RAG_MAXB;
-  if (rag) {
-    rag_build(rtc, rlv, a.lens, a.lmul, L, 0, L, a.B, BN, tid);
-    __syncthreads();
-  }
-  const int ntiles = __builtin_amdgcn_readfirstlane(rag ? rtc[a.B - 1] : a.B * ntn);  // scalar: so is the tile walk
-  const int G = gridDim.x, g = blockIdx.x;
-  const int gl = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
-  const int nmine = gl < ntiles ? (ntiles - gl + G - 1) / G : 0;
-  if (nmine == 0) return;
-  for (int i = tid; i < C; i += NT) {
-    reinterpret_cast<float*>(smem + PAR_OFF)[i] = a.b1[i];
-    reinterpret_cast<float*>(smem + PAR_OFF)[C + i] = a.b2[i];
-  }
-  __syncthreads();
+  PairWalk tiles;
+  if (!tiles.init(a, smem + RAG_OFF, BN, tid)) return;
+  const int nmine = tiles.nmine;
+  pair_load_bias<C, NT>(reinterpret_cast<float*>(smem + PAR_OFF), a, tid);
 
   int issued = 0, xmk = 0;
   int wmk[NWS] = {};
   const int ns = (k + 1) / 2;    // steps per conv
   const int S = nmine * 2 * ns;  // weight steps of this workgroup
-  RagWalk walk;
-  auto tile_of = [&](int ti) {  // (utterance, first frame, valid frames) of tile ti
-    const int tile = __builtin_amdgcn_readfirstlane(gl + ti * G);
-    if (rag) return walk.at(rtc, rlv, a.B, BN, tile);
-    RagTile t;
-    t.b = tile / ntn;
-    t.n0 = (tile - t.b * ntn) * BN;
-    t.lv = L;
-    return t;
-  };
   RagTile nxt;  // the tile stage_x staged last (the next tile of the loop)
   // VP_BUF: this lane's byte offsets within a weight piece (row 8 wave + lrow of a tap block) and a row piece (row
   // lrow of 8); the 16-byte unit is swizzled by row & 6 = lrow & 6 in both
@@ -161,7 +97,7 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const bf16* base = w + (size_t)min(2 * m + u, k - 1) * C * 64;
-      vp_glds16(base + r * 64 + (lp ^ (r & 6)) * 8, smem + W_OFF + (s % NWS) * WSLOT + u * TAPW + wave * 1024);
+      glds16(base + r * 64 + (lp ^ (r & 6)) * 8, smem + W_OFF + (s % NWS) * WSLOT + u * TAPW + wave * 1024);
     }
     issued += 2;
     wmk[s % NWS] = issued;
@@ -186,14 +122,14 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
         const bf16* base = w + (size_t)min(2 * m + u, k - 1) * C * 64;
         int off = r * 64 + (lp ^ (r & 6)) * 8;
         asm volatile("" : "+v"(off));
-        vp_glds16(base + off, smem + so + u * TAPW);
+        glds16(base + off, smem + so + u * TAPW);
       }
     }
   };
   const bf16* sx_xb = a.x;
   int sx_f0 = 0, sx_lv = 0;
   auto stage_x_begin = [&](int ti) {
-    nxt = tile_of(K > 0 ? min(ti, nmine - 1) : ti);  // K > 0: past the last tile a phantom copy of it (never read)
+    nxt = tiles.at(K > 0 ? min(ti, nmine - 1) : ti);  // K > 0: past the last tile a phantom copy of it (never read)
     sx_xb = a.x + (size_t)__builtin_amdgcn_readfirstlane(nxt.b) * L * C;
     sx_f0 = __builtin_amdgcn_readfirstlane(nxt.n0 - HALO2 - h1), sx_lv = __builtin_amdgcn_readfirstlane(nxt.lv);
   };
@@ -211,7 +147,7 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
     const int q = lp ^ (r & 6);
     const int f = sx_f0 + r;
     const bool ok = r < NF1 + 2 * h1 && f >= 0 && f < sx_lv;
-    vp_glds16(ok ? sx_xb + (size_t)f * C + q * 8 : a.zero + q * 8, smem + j * 1024);
+    glds16(ok ? sx_xb + (size_t)f * C + q * 8 : a.zero + q * 8, smem + j * 1024);
   };
   auto stage_x = [&](int ti) {  // raw rows of tile ti: row r = frame n0 - HALO2 - h1 + r
     stage_x_begin(ti);
@@ -221,11 +157,6 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
     xmk = issued;
   };
 
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
   const int ha = l16 & 6;
 
   f32x4 acc[4][FN];
@@ -286,8 +217,8 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
       if constexpr ((VPAIR_EXP & 16) == 0) {  // timing experiment 16: no per-step wait / barrier (wrong results)
         // this step's weights (staged two steps ago) and the next step's, whose first K-slice is read at this
         // step's end
-        vp_wait_vmcnt(issued - wmk[(more ? s + 1 : s) % NWS]);
-        vp_barrier();
+        wait_vmcnt(issued - wmk[(more ? s + 1 : s) % NWS]);
+        lds_barrier();
       }
       VP_TS(6);
       if (s + NWS - 1 < S) stage_w(s + NWS - 1);
@@ -313,7 +244,7 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
   };
   // K > 0: conv CV (0: conv1 steps 0 .. NS-1 of the tile, 1: conv2 steps NS .. S-1) unrolled: ring slots from the
   // tile's slot base sb (S % 3 != 0 rotates it per tile), counted waits (VpkSched), step barriers without an lgkmcnt
-  // drain (vp_step_barrier) except a conv's first, which also publishes the activated rows / T
+  // drain (step_barrier, mt_pipe.h) except a conv's first, which also publishes the activated rows / T
   using SCH = VpSched<EF, K>;
   auto slot_of = [&](int sb, int q) __attribute__((always_inline)) {  // ring slot of tile step q (q may pass S)
     const int v = sb + q % NWS;
@@ -333,8 +264,8 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
       } else {
         vc_wait_vmcnt<SCH::wait(st)>();
       }
-      if constexpr (m == 0) vp_barrier();
-      else vp_step_barrier();
+      if constexpr (m == 0) lds_barrier();
+      else step_barrier();
       VP_TS(6);
       stage_w_ct(std::integral_constant<int, st + NWS - 1>{}, slot_of(sb, st + NWS - 1));
       const int sl = slot_of(sb, st);
@@ -379,10 +310,10 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
       if (ti == 0) vc_wait_vmcnt<SCH::xwait_first>();
       else vc_wait_vmcnt<SCH::xwait>();
     } else {
-      vp_wait_vmcnt(issued - xmk);
+      wait_vmcnt(issued - xmk);
     }
     VP_TS(0);
-    vp_barrier();
+    lds_barrier();
     VP_TS(1);
     u32x4 rv[2][FN], yv[2][FN];  // residual x and (VE_ACCUM) old xs of this lane's outputs
 #pragma unroll
@@ -393,7 +324,7 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
         rv[fp][fn] = *reinterpret_cast<const u32x4*>(smem + r * 128 + ((q ^ (r & 6)) * 16));
       }
-    vp_barrier();
+    lds_barrier();
     VP_TS(2);
 #pragma unroll
     for (int i = 0; i < ((VPAIR_EXP & 1) ? 0 : XROWS * 8 / NT); ++i) {
@@ -455,11 +386,8 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
           o[h][0] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][0], acc[fm][fn][1]} + f32x2{b4[0], b4[1]}, a.slope) : 0u;
           o[h][1] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][2], acc[fm][fn][3]} + f32x2{b4[2], b4[3]}, a.slope) : 0u;
         }
-        swap16(o[0][0], o[1][0]);
-        swap16(o[0][1], o[1][1]);
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
-        *reinterpret_cast<u32x4*>(smem + T_OFF + j * 128 + ((q ^ (j & 6)) * 16)) =
-            u32x4{o[0][0], o[0][1], o[1][0], o[1][1]};
+        *reinterpret_cast<u32x4*>(smem + T_OFF + j * 128 + ((q ^ (j & 6)) * 16)) = pack16(o);
       }
     VP_TS(5);
     // ---- 3. conv2 ----
@@ -485,7 +413,7 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
     // epilogue: + b2 + x [+ xs] [/ nk] -> y [, lrelu(y) -> y2]
     if constexpr ((EF & VE_ACCUM) != 0) {
       if constexpr (K > 0) vc_wait_vmcnt<SCH::accwait>();
-      else vp_wait_vmcnt(issued - ymk);
+      else wait_vmcnt(issued - ymk);
 #pragma unroll
       for (int fp = 0; fp < 2; ++fp)
 #pragma unroll
@@ -501,62 +429,40 @@ __global__ __launch_bounds__(NT) void vpair_kernel(VPairArgs a) {
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
         const int i = wave * WNC + fn * 16 + l16;  // output frame n0 + i
-        uint32_t rx0 = rv[fp][fn][0], rx1 = rv[fp][fn][1], ry0 = rv[fp][fn][2], ry1 = rv[fp][fn][3];
-        swap16(rx0, ry0);  // back to the accumulator layout
-        swap16(rx1, ry1);
-        uint32_t yx0 = 0, yx1 = 0, yy0 = 0, yy1 = 0;
-        if constexpr ((EF & VE_ACCUM) != 0) {
-          yx0 = yv[fp][fn][0], yx1 = yv[fp][fn][1], yy0 = yv[fp][fn][2], yy1 = yv[fp][fn][3];
-          swap16(yx0, yy0);
-          swap16(yx1, yy1);
-        }
-        uint32_t o1[2][2], o2[2][2];
+        uint32_t rr[2][2], yy[2][2] = {}, o1[2][2], o2[2][2];  // [X|Y][dword]: x, old xs, y and its activated copy
+        unpack16(rv[fp][fn], rr);  // back to the accumulator layout
+        if constexpr ((EF & VE_ACCUM) != 0) unpack16(yv[fp][fn], yy);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int fm = 2 * fp + h;
           const f32x4 b4 = *reinterpret_cast<const f32x4*>(par + C + fm * 16 + 4 * g4);
-          const uint32_t rr[2] = {h ? ry0 : rx0, h ? ry1 : rx1};
-          const uint32_t yy[2] = {h ? yy0 : yx0, h ? yy1 : yx1};
-          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu, two channels per packed op
+          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu (res_out, mt_vconv.h), two channels per packed op
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             if constexpr ((VPAIR_EXP & 4) != 0) {  // timing experiment: no epilogue arithmetic (wrong results)
-              o1[h][u] = o2[h][u] = __float_as_uint(acc[fm][fn][2 * u] + acc[fm][fn][2 * u + 1]) ^ rr[u] ^ yy[u];
+              o1[h][u] = o2[h][u] = __float_as_uint(acc[fm][fn][2 * u] + acc[fm][fn][2 * u + 1]) ^ rr[h][u] ^ yy[h][u];
               continue;
             }
-            f32x2 v = f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]} + f32x2{b4[2 * u], b4[2 * u + 1]};
-            v = v + unpk_bf16(rr[u]);
-            if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-            if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
-            o1[h][u] = pk_bf16(v);
-            o2[h][u] = lrelu_pk(o1[h][u], a.slope);  // the stored state's activated copy
+            res_out<EF | VE_RESID>(f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]}, f32x2{b4[2 * u], b4[2 * u + 1]}, rr[h][u],
+                                   yy[h][u], a.div, a.slope, o1[h][u], o2[h][u]);
           }
         }
-        swap16(o1[0][0], o1[1][0]);
-        swap16(o1[0][1], o1[1][1]);
+        const u32x4 y = pack16(o1);
         if constexpr (VP_BUF) {
           // the utterance's [L][C] output as a buffer: frames past L fall outside it (store dropped); the discarded
           // frames i >= BN (the last wave's last fragment) get an offset past any range; every lane still stores
           const bool keep = !(fn == FN - 1 && wave == 7);
           const unsigned vo = keep ? (unsigned)(((n0 + i) * C + fp * 32 + ch16) * 2) : 0x80000000u;
           if constexpr ((EF & VE_Y2ONLY) == 0)
-            buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
-          if constexpr ((EF & VE_DUAL) != 0) {
-            swap16(o2[0][0], o2[1][0]);
-            swap16(o2[0][1], o2[1][1]);
-            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
-          }
+            buf_store16<SP>(y, yr, vo);
+          if constexpr ((EF & VE_DUAL) != 0) buf_store16<SP>(pack16(o2), y2r, vo);
           continue;
         }
         const bool ok = i < BN && n0 + i < L;
         const size_t o = ((size_t)b * L + n0 + i) * C + fp * 32 + ch16;
         if constexpr ((EF & VE_Y2ONLY) == 0)
-          *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
-        if constexpr ((EF & VE_DUAL) != 0) {
-          swap16(o2[0][0], o2[1][0]);
-          swap16(o2[0][1], o2[1][1]);
-          *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]};
-        }
+          *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = y;
+        if constexpr ((EF & VE_DUAL) != 0) *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = pack16(o2);
       }
     issued += 2 * FN * ((EF & VE_DUAL) && !(EF & VE_Y2ONLY) ? 2 : 1);
     VP_TS(9);
@@ -599,50 +505,25 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
   const int g4 = lane >> 4, l16 = lane & 15, lrow = lane >> 3, lp = lane & 7;
   const int d = a.dil, L = a.L;
   const int h1 = d;  // k = 3: h1 = d, h2 = 1 = HALO2
-  const int ntn = (L + BN - 1) / BN;
-  // ragged batch: the live tiles of each utterance (mt_ragged.h)
-  const bool rag = a.lens != nullptr;
-  int* rtc = reinterpret_cast<int*>(smem + G3::RAG_OFF);
-  int* rlv = rtc + RAG_MAXB;
-  if (rag) {
-    rag_build(rtc, rlv, a.lens, a.lmul, L, 0, L, a.B, BN, tid);
-    __syncthreads();
-  }
-  const int ntiles = __builtin_amdgcn_readfirstlane(rag ? rtc[a.B - 1] : a.B * ntn);  // scalar: so is the tile walk
-  const int G = gridDim.x, g = blockIdx.x;
-  const int gl = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
-  const int nmine = gl < ntiles ? (ntiles - gl + G - 1) / G : 0;
-  if (nmine == 0) return;
-  for (int i = tid; i < C; i += NT) {
-    reinterpret_cast<float*>(smem + K3_PAR_OFF)[i] = a.b1[i];
-    reinterpret_cast<float*>(smem + K3_PAR_OFF)[C + i] = a.b2[i];
-  }
-  __syncthreads();
+  PairWalk tiles;
+  if (!tiles.init(a, smem + G3::RAG_OFF, BN, tid)) return;
+  const int nmine = tiles.nmine;
+  pair_load_bias<C, NT>(reinterpret_cast<float*>(smem + K3_PAR_OFF), a, tid);
 
   int issued = 0;
   int xmk[2] = {0, 0};
-  RagWalk walk;
-  auto tile_of = [&](int ti) {  // (utterance, first frame, valid frames) of tile ti
-    const int tile = __builtin_amdgcn_readfirstlane(gl + ti * G);
-    if (rag) return walk.at(rtc, rlv, a.B, BN, tile);
-    RagTile t;
-    t.b = tile / ntn;
-    t.n0 = (tile - t.b * ntn) * BN;
-    t.lv = L;
-    return t;
-  };
   RagTile nxt;  // the tile stage_x staged last (the next tile of the loop)
   // both convs' 3 taps: DMA j moves rows (j & 7) * 8 .. + 7 of tap j / 8 (conv (j / 8) / 3)
   for (int j = wave; j < 48; j += 8) {
     const int tp = j >> 3, r = (j & 7) * 8 + lrow;
     const bf16* w = (tp < 3 ? a.w1 : a.w2) + (size_t)(tp % 3) * C * 64;
-    vp_glds16(w + r * 64 + (lp ^ (r & 6)) * 8, smem + K3_W_OFF + tp * TAPW + (j & 7) * 1024);
+    glds16(w + r * 64 + (lp ^ (r & 6)) * 8, smem + K3_W_OFF + tp * TAPW + (j & 7) * 1024);
     ++issued;
   }
   const bf16* sx_xb = a.x;
   int sx_f0 = 0, sx_R1 = 0, sx_lv = 0, sx_buf = 0;
   auto stage_x_begin = [&](int ti) {
-    nxt = tile_of(ti);
+    nxt = tiles.at(ti);
     const bool live = ti < nmine;
     sx_xb = a.x + (size_t)(live ? nxt.b : 0) * L * C;
     sx_f0 = nxt.n0 - HALO2 - h1, sx_R1 = live ? NF1 + 2 * h1 : 0, sx_lv = nxt.lv;
@@ -653,7 +534,7 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
     const int q = lp ^ (r & 6);
     const int f = sx_f0 + r;
     const bool ok = r < sx_R1 && f >= 0 && f < sx_lv;
-    vp_glds16(ok ? sx_xb + (size_t)f * C + q * 8 : a.zero + q * 8, smem + sx_buf * K3_XBUF + j * 1024);
+    glds16(ok ? sx_xb + (size_t)f * C + q * 8 : a.zero + q * 8, smem + sx_buf * K3_XBUF + j * 1024);
     ++issued;
   };
   auto stage_x = [&](int ti) {  // raw rows of tile ti into buffer ti & 1: row r = frame n0 - HALO2 - h1 + r
@@ -662,11 +543,6 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
     xmk[DB ? ti & 1 : 0] = issued;
   };
 
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
   const int ha = l16 & 6;
   f32x4 acc[4][FN];
   struct Frag {
@@ -745,9 +621,9 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
     // ---- 1. rows landed (the first wait also covers the weights); old-xs loads, then the next tile's rows
     // into the other buffer (vmcnt retires in order); residual rows; in-place lrelu ----
     VP_TS(10);
-    vp_wait_vmcnt(issued - xmk[DB ? ti & 1 : 0]);
+    wait_vmcnt(issued - xmk[DB ? ti & 1 : 0]);
     VP_TS(0);
-    vp_barrier();
+    lds_barrier();
     VP_TS(1);
     u32x4 rv[2][FN], yv[2][FN];
     int ymk = 0;
@@ -774,7 +650,7 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
         rv[fp][fn] = *reinterpret_cast<const u32x4*>(xs + r * 128 + ((q ^ (r & 6)) * 16));
       }
-    vp_barrier();
+    lds_barrier();
     VP_TS(2);
     for (int e = tid; e < ((VPAIR_EXP & 1) ? 0 : K3_XBUF / 16); e += NT) {
       u32x4 v = *reinterpret_cast<const u32x4*>(xs + e * 16);
@@ -782,7 +658,7 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
       for (int w = 0; w < 4; ++w) v[w] = lrelu_pk(v[w], a.slope);
       *reinterpret_cast<u32x4*>(xs + e * 16) = v;
     }
-    vp_barrier();
+    lds_barrier();
     VP_TS(3);
     // ---- 2. conv1 -> T ----
     conv(0, xs, wave * WNC + l16, d, spread);
@@ -808,21 +684,18 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
           o[h][0] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][0], acc[fm][fn][1]} + f32x2{b4[0], b4[1]}, a.slope) : 0u;
           o[h][1] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][2], acc[fm][fn][3]} + f32x2{b4[2], b4[3]}, a.slope) : 0u;
         }
-        swap16(o[0][0], o[1][0]);
-        swap16(o[0][1], o[1][1]);
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
-        *reinterpret_cast<u32x4*>(smem + K3_T_OFF + j * 128 + ((q ^ (j & 6)) * 16)) =
-            u32x4{o[0][0], o[0][1], o[1][0], o[1][1]};
+        *reinterpret_cast<u32x4*>(smem + K3_T_OFF + j * 128 + ((q ^ (j & 6)) * 16)) = pack16(o);
       }
     VP_TS(5);
-    vp_barrier();  // T published (single buffer: every wave is past conv1's reads of the rows)
+    lds_barrier();  // T published (single buffer: every wave is past conv1's reads of the rows)
     if constexpr (!DB) stage_x(ti + 1);
     VP_TS(6);
     // ---- 3. conv2 -> y ----
     conv(3, smem + K3_T_OFF, wave * WNC + l16, 1, spread);
     VP_TS(7);
     if constexpr ((EF & VE_ACCUM) != 0) {
-      vp_wait_vmcnt(issued - ymk);
+      wait_vmcnt(issued - ymk);
 #pragma unroll
       for (int fp = 0; fp < 2; ++fp)
 #pragma unroll
@@ -834,60 +707,39 @@ __global__ __launch_bounds__(NT) void vpair3_kernel(VPairArgs a) {
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
         const int i = wave * WNC + fn * 16 + l16;
-        uint32_t rx0 = rv[fp][fn][0], rx1 = rv[fp][fn][1], ry0 = rv[fp][fn][2], ry1 = rv[fp][fn][3];
-        swap16(rx0, ry0);
-        swap16(rx1, ry1);
-        uint32_t yx0 = 0, yx1 = 0, yy0 = 0, yy1 = 0;
-        if constexpr ((EF & VE_ACCUM) != 0) {
-          yx0 = yv[fp][fn][0], yx1 = yv[fp][fn][1], yy0 = yv[fp][fn][2], yy1 = yv[fp][fn][3];
-          swap16(yx0, yy0);
-          swap16(yx1, yy1);
-        }
-        uint32_t o1[2][2], o2[2][2];
+        uint32_t rr[2][2], yy[2][2] = {}, o1[2][2], o2[2][2];  // [X|Y][dword]: x, old xs, y and its activated copy
+        unpack16(rv[fp][fn], rr);  // back to the accumulator layout
+        if constexpr ((EF & VE_ACCUM) != 0) unpack16(yv[fp][fn], yy);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int fm = 2 * fp + h;
           const f32x4 b4 = *reinterpret_cast<const f32x4*>(par + C + fm * 16 + 4 * g4);
-          const uint32_t rr[2] = {h ? ry0 : rx0, h ? ry1 : rx1};
-          const uint32_t yy[2] = {h ? yy0 : yx0, h ? yy1 : yx1};
-          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu, two channels per packed op
+          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu (res_out, mt_vconv.h), two channels per packed op
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             if constexpr ((VPAIR_EXP & 4) != 0) {  // timing experiment: no epilogue arithmetic (wrong results)
-              o1[h][u] = o2[h][u] = __float_as_uint(acc[fm][fn][2 * u] + acc[fm][fn][2 * u + 1]) ^ rr[u] ^ yy[u];
+              o1[h][u] = o2[h][u] = __float_as_uint(acc[fm][fn][2 * u] + acc[fm][fn][2 * u + 1]) ^ rr[h][u] ^ yy[h][u];
               continue;
             }
-            f32x2 v = f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]} + f32x2{b4[2 * u], b4[2 * u + 1]};
-            v = v + unpk_bf16(rr[u]);
-            if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-            if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
-            o1[h][u] = pk_bf16(v);
-            o2[h][u] = lrelu_pk(o1[h][u], a.slope);  // the stored state's activated copy
+            res_out<EF | VE_RESID>(f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]}, f32x2{b4[2 * u], b4[2 * u + 1]}, rr[h][u],
+                                   yy[h][u], a.div, a.slope, o1[h][u], o2[h][u]);
           }
         }
-        swap16(o1[0][0], o1[1][0]);
-        swap16(o1[0][1], o1[1][1]);
+        const u32x4 y = pack16(o1);
         const bool ok = i < BN && n0 + i < L;
         if constexpr (SP != ST_PLAIN) {
           // the same stores through the utterance's [L][C] output as a buffer (the ring kernel's form): a store that is
           // not ok gets an offset past any range and is dropped; every lane still stores
           const size_t ub = (size_t)__builtin_amdgcn_readfirstlane(b) * L * C;
           const unsigned vo = ok ? (unsigned)(((n0 + i) * C + fp * 32 + ch16) * 2) : 0x80000000u;
-          buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, buf_rsrc(a.y + ub, (unsigned)L * (C * 2)), vo);
-          if constexpr ((EF & VE_DUAL) != 0) {
-            swap16(o2[0][0], o2[1][0]);
-            swap16(o2[0][1], o2[1][1]);
-            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, buf_rsrc(a.y2 + ub, (unsigned)L * (C * 2)), vo);
-          }
+          buf_store16<SP>(y, buf_rsrc(a.y + ub, (unsigned)L * (C * 2)), vo);
+          if constexpr ((EF & VE_DUAL) != 0)
+            buf_store16<SP>(pack16(o2), buf_rsrc(a.y2 + ub, (unsigned)L * (C * 2)), vo);
           continue;
         }
         const size_t o = ((size_t)b * L + n0 + i) * C + fp * 32 + ch16;
-        *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
-        if constexpr ((EF & VE_DUAL) != 0) {
-          swap16(o2[0][0], o2[1][0]);
-          swap16(o2[0][1], o2[1][1]);
-          *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]};
-        }
+        *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = y;
+        if constexpr ((EF & VE_DUAL) != 0) *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = pack16(o2);
       }
     issued += 2 * FN * ((EF & VE_DUAL) ? 2 : 1);
     VP_TS(9);
@@ -918,62 +770,29 @@ bool vpair_supported(int C_, int k, int d) {
   return C_ == C && k >= 2 && (k - 1) / 2 <= HALO2 && NF1 + d * (k - 1) <= XROWS;
 }
 
-static int vp_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 int launch_vpair(int ef, const VPairArgs& a, hipStream_t st) {
-  MT_REQUIRE(!(ef & VE_DIV) || div_rn_ok(a.div), "vpair: VE_DIV divisor %g outside the exactly-checked set (div_rn)", (double)a.div);
-  MT_REQUIRE(a.x && a.w1 && a.w2 && a.b1 && a.b2 && a.y && a.zero && a.trash && a.B > 0 && a.L > 0,
-             "vpair: null argument / empty");
-  MT_REQUIRE(vpair_supported(C, a.taps, a.dil) && a.taps % 2 == 1, "vpair: k %d d %d", a.taps, a.dil);
-  MT_REQUIRE(!(ef & VE_DUAL) || a.y2, "vpair: y2");
-  MT_REQUIRE(a.y != a.x, "vpair: y must not alias x (neighbour tiles read x's halo)");
-  // k = 3: resident weights; MT_VPAIR3 (A/B knob, read once) picks the geometry: "2d" (default) 2 fragments per
-  // wave + double-buffered rows, "2" / "3" 2 / 3 fragments single-buffered, "0" the weight-ring kernel
-  static const int k3mode = [] {
+  if (pair_check("vpair", ef, a, vpair_supported(C, a.taps, a.dil) && a.taps % 2 == 1)) return -1;
+  // k = 3: resident weights, 2 fragments per wave and double-buffered rows (vpair3_kernel<E, 2, true>); MT_VPAIR3=0
+  // (A/B knob, read once) runs them on the weight-ring kernel instead
+  static const bool k3on = [] {
     const char* e = getenv("MT_VPAIR3");
-    return !e ? 1 : !strcmp(e, "0") ? 0 : !strcmp(e, "2") ? 2 : !strcmp(e, "3") ? 3 : 1;
+    return !(e && !strcmp(e, "0"));
   }();
-  const bool k3 = a.taps == 3 && a.dil <= 8 && k3mode != 0;
+  const bool k3 = a.taps == 3 && a.dil <= 8 && k3on;
   if (k3 || !(ef & VE_DUAL)) ef &= ~VE_Y2ONLY;  // only the ring kernel drops the raw store (VE_Y2ONLY)
-  const int bn = !k3 ? BN : k3mode == 3 ? K3G<3, false>::BN : K3G<2, true>::BN;
-  const long ntiles = (long)a.B * ((a.L + bn - 1) / bn);
-  const int G = (int)std::min<long>(ntiles, vp_cu_count());
-  // probe: the pair is two of the family's convs (SURVEY §8d algorithmic FLOPs and layer-boundary bytes)
-  const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
-  const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
-  // the store policy (mt_common.h) on the default kernels: the k = 3 "2d" geometry and the compile-time K ring
+  // the store policy (mt_common.h) on the default kernels: the k = 3 geometry and the compile-time K ring
   const bool wt = store_policy() == ST_WT;
-  probe_begin(PROBE_VCONV, st);
-  if (k3) {
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(G), dim3(NT), 0, st, a); };
-#define MT_VP3(E)                                                       \
-  (k3mode == 3 ? go(vpair3_kernel<E, 3, false>) : k3mode == 2 ? go(vpair3_kernel<E, 2, false>) \
-   : wt        ? go(vpair3_kernel<E, 2, true, ST_WT>)                                           \
-               : go(vpair3_kernel<E, 2, true>))
-    switch (ef) {
-      case 0: MT_VP3(0); break;
-      case VE_ACCUM: MT_VP3(VE_ACCUM); break;
-      case VE_ACCUM | VE_DIV: MT_VP3(VE_ACCUM | VE_DIV); break;
-      case VE_ACCUM | VE_DIV | VE_DUAL: MT_VP3(VE_ACCUM | VE_DIV | VE_DUAL); break;
-      case VE_DIV: MT_VP3(VE_DIV); break;
-      case VE_DIV | VE_DUAL: MT_VP3(VE_DIV | VE_DUAL); break;
-      default: set_error("vpair: epilogue %d not compiled in", ef); return -1;
-    }
-#undef MT_VP3
-  } else {
-    // k = 7 / 11 (the vocoder's): the compile-time K loop; other kernel sizes the runtime-k loop (same bits)
-    const bool ctk = (vpair_kernels() & VPK_CTK) != 0;
-    auto ring = [&](auto efc) {
-      constexpr int E = decltype(efc)::value;
+  // k = 7 / 11 (the vocoder's): the compile-time K loop; other kernel sizes the runtime-k loop (same bits)
+  const bool ctk = (vpair_kernels() & VPK_CTK) != 0;
+  return pair_launch("vpair", C, k3 ? K3G<2, true>::BN : BN, ef, a, st, PROBE_TAG_VPAIR, [&](int G) {
+    if (k3)
+      return pair_with_ef(ef, [&](auto ec) {
+        constexpr int E = decltype(ec)::value;
+        if (wt) hipLaunchKernelGGL((vpair3_kernel<E, 2, true, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vpair3_kernel<E, 2, true>), dim3(G), dim3(NT), 0, st, a);
+      });
+    return pair_with_ef<VE_Y2ONLY>(ef, [&](auto ec) {
+      constexpr int E = decltype(ec)::value;
       if (!ctk) hipLaunchKernelGGL((vpair_kernel<E>), dim3(G), dim3(NT), 0, st, a);
       else if (a.taps == 7) {
         (void)VpkReg<2, VpSched<E, 7>, E>::reg;
@@ -985,25 +804,8 @@ int launch_vpair(int ef, const VPairArgs& a, hipStream_t st) {
         else hipLaunchKernelGGL((vpair_kernel<E, 11>), dim3(G), dim3(NT), 0, st, a);
       }
       else hipLaunchKernelGGL((vpair_kernel<E>), dim3(G), dim3(NT), 0, st, a);
-    };
-    switch (ef) {
-      case 0: ring(std::integral_constant<int, 0>{}); break;
-      case VE_ACCUM: ring(std::integral_constant<int, VE_ACCUM>{}); break;
-      case VE_ACCUM | VE_DIV: ring(std::integral_constant<int, VE_ACCUM | VE_DIV>{}); break;
-      case VE_ACCUM | VE_DIV | VE_DUAL: ring(std::integral_constant<int, VE_ACCUM | VE_DIV | VE_DUAL>{}); break;
-      case VE_ACCUM | VE_DIV | VE_DUAL | VE_Y2ONLY:
-        ring(std::integral_constant<int, VE_ACCUM | VE_DIV | VE_DUAL | VE_Y2ONLY>{});
-        break;
-      case VE_DIV: ring(std::integral_constant<int, VE_DIV>{}); break;
-      case VE_DIV | VE_DUAL: ring(std::integral_constant<int, VE_DIV | VE_DUAL>{}); break;
-      default: set_error("vpair: epilogue %d not compiled in", ef); return -1;
-    }
-  }
-  MT_CHECK_HIP(hipGetLastError());
-  probe_end(PROBE_VCONV, st, flops, bytes, PROBE_TAG_VPAIR);
-  const int rec[VCLOG_FIELDS] = {ef | 0x10000, C, bn, 0, (int)ntiles, G, a.taps, C, C, a.B, a.L};
-  vclog_record(rec);
-  return 0;
+    });
+  });
 }
 
 VP_TS_BINDER(vpair_ts_bind)

@@ -69,44 +69,6 @@ static_assert(32 * XPW <= XROWS, "fixed row staging fits the X planes");
 template <int EF, int K>
 using Vp128Sched = VpkSched<EF, 2 * (K > 0 ? K : 1), XPW, FN, (VP128_XSP < 2 * K ? VP128_XSP : 2 * (K > 0 ? K : 1)), NWS>;
 
-namespace {
-
-__device__ __forceinline__ void glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-__device__ __forceinline__ void wait_vmcnt(int n) {
-  if (n < 7) {
-    if (n < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (n < 4) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else if (n < 15) {
-    if (n < 10) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  } else {
-    if (n < 23) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    else if (n < 31) asm volatile("s_waitcnt vmcnt(23)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-  }
-}
-
-__device__ __forceinline__ void barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-// a compile-time K-loop step's barrier (mt_vpair.hip vp_step_barrier): no LDS write in flight, no lgkmcnt drain
-__device__ __forceinline__ void step_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-}  // namespace
-
 // K > 0: the compile-time K loop (k = K): steps unrolled, ring slots and vmcnt counts constants (VpkSched), step
 // barriers without an lgkmcnt drain except each conv's first, phantom prefetches past the workgroup's last tile
 template <int EF, int K = 0, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h)
@@ -122,40 +84,15 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
   const int BN = NF1 - 2 * h2;  // output frames per tile
   const int R1 = NF1 + 2 * h1;  // staged rows per plane
   const int nxi = (R1 + 7) / 8; // DMA instructions per plane
-  const int ntn = (L + BN - 1) / BN;
-  // ragged batch: the live tiles of each utterance (mt_ragged.h)
-  const bool rag = a.lens != nullptr;
-  int* rtc = reinterpret_cast<int*>(smem + RAG_OFF);
-  int* rlv = rtc + RAG_MAXB;
-  if (rag) {
-    rag_build(rtc, rlv, a.lens, a.lmul, L, 0, L, a.B, BN, tid);
-    __syncthreads();
-  }
-  const int ntiles = __builtin_amdgcn_readfirstlane(rag ? rtc[a.B - 1] : a.B * ntn);  // scalar: so is the tile walk
-  const int G = gridDim.x, g = blockIdx.x;
-  const int gl = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
-  const int nmine = gl < ntiles ? (ntiles - gl + G - 1) / G : 0;
-  if (nmine == 0) return;
-  for (int i = tid; i < C; i += NT) {
-    reinterpret_cast<float*>(smem + PAR_OFF)[i] = a.b1[i];
-    reinterpret_cast<float*>(smem + PAR_OFF)[C + i] = a.b2[i];
-  }
-  __syncthreads();
+  PairWalk tiles;
+  if (!tiles.init(a, smem + RAG_OFF, BN, tid)) return;
+  const int nmine = tiles.nmine;
+  pair_load_bias<C, NT>(reinterpret_cast<float*>(smem + PAR_OFF), a, tid);
 
   int issued = 0, xmk = 0;
   int wmk[NWS] = {};
   const int ns = 2 * k;          // steps per conv: (chunk, tap), chunk-major
   const int S = nmine * 2 * ns;  // weight steps of this workgroup
-  RagWalk walk;
-  auto tile_of = [&](int ti) {  // (utterance, first frame, valid frames) of tile ti
-    const int tile = __builtin_amdgcn_readfirstlane(gl + ti * G);
-    if (rag) return walk.at(rtc, rlv, a.B, BN, tile);
-    RagTile t;
-    t.b = tile / ntn;
-    t.n0 = (tile - t.b * ntn) * BN;
-    t.lv = L;
-    return t;
-  };
   RagTile nxt;  // the tile stage_x staged last (the next tile of the loop)
   // VP128_BUF: this lane's byte offsets within a weight piece (row 16 wave + lrow of the step's block; + 8 rows for
   // the second piece) and a row piece (row lrow of 8 of one plane); the 16-byte unit is swizzled by lrow & 6
@@ -198,7 +135,7 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
   const bf16* sx_xb = a.x;
   int sx_f0 = 0, sx_lv = 0;
   auto stage_x_begin = [&](int ti) {
-    nxt = tile_of(K > 0 ? min(ti, nmine - 1) : ti);  // K > 0: past the last tile a phantom copy of it (never read)
+    nxt = tiles.at(K > 0 ? min(ti, nmine - 1) : ti);  // K > 0: past the last tile a phantom copy of it (never read)
     sx_xb = a.x + (size_t)__builtin_amdgcn_readfirstlane(nxt.b) * L * C;
     sx_f0 = __builtin_amdgcn_readfirstlane(nxt.n0 - h2 - h1), sx_lv = __builtin_amdgcn_readfirstlane(nxt.lv);
   };
@@ -232,11 +169,6 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
     }
   };
 
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
-  };
   const int ha = l16 & 6;
 
   f32x4 acc[4][FN];
@@ -283,7 +215,7 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
       if (s % (2 * ns) < ns) VP_TS(4); else VP_TS(7);
 #endif
       wait_vmcnt(issued - wmk[(more ? s + 1 : s) % NWS]);  // this step's weights and the next step's
-      barrier();
+      lds_barrier();
       VP_TS(6);
       if (s + NWS - 1 < S) stage_w(s + NWS - 1);
       const int sl = s % NWS;
@@ -327,7 +259,7 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
       } else {
         vc_wait_vmcnt<SCH::wait(st)>();
       }
-      if constexpr (m == 0) barrier();
+      if constexpr (m == 0) lds_barrier();
       else step_barrier();
       VP_TS(6);
       stage_w_ct(std::integral_constant<int, st + NWS - 1>{}, slot_of(sb, st + NWS - 1));
@@ -370,7 +302,7 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
       wait_vmcnt(issued - xmk);
     }
     VP_TS(0);
-    barrier();
+    lds_barrier();
     VP_TS(1);
     u32x4 rv[2][FN], yv[2][FN];  // residual x and (VE_ACCUM) old xs of this lane's outputs
 #pragma unroll
@@ -381,7 +313,7 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
         rv[fp][fn] = *reinterpret_cast<const u32x4*>(xpl + r * 128 + ((q ^ (r & 6)) * 16));
       }
-    barrier();
+    lds_barrier();
     VP_TS(2);
     for (int e = tid; e < 2 * XROWS * 8; e += NT) {
       u32x4 v = *reinterpret_cast<const u32x4*>(smem + X_OFF + e * 16);
@@ -435,11 +367,8 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
           o[h][0] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][0], acc[fm][fn][1]} + f32x2{b4[0], b4[1]}, a.slope) : 0u;
           o[h][1] = ok ? lrelu_pk_f(f32x2{acc[fm][fn][2], acc[fm][fn][3]} + f32x2{b4[2], b4[3]}, a.slope) : 0u;
         }
-        swap16(o[0][0], o[1][0]);
-        swap16(o[0][1], o[1][1]);
         const int q = fp * 4 + (g4 & 1) * 2 + (g4 >> 1);
-        *reinterpret_cast<u32x4*>(smem + T_OFF + wm * TPL + j * 128 + ((q ^ (j & 6)) * 16)) =
-            u32x4{o[0][0], o[0][1], o[1][0], o[1][1]};
+        *reinterpret_cast<u32x4*>(smem + T_OFF + wm * TPL + j * 128 + ((q ^ (j & 6)) * 16)) = pack16(o);
       }
     VP_TS(5);
     // ---- 3. conv2 ----
@@ -479,55 +408,33 @@ __global__ __launch_bounds__(NT) void vpair128_kernel(VPairArgs a) {
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
         const int i = wn * WNC + fn * 16 + l16;  // output frame n0 + i
-        uint32_t rx0 = rv[fp][fn][0], rx1 = rv[fp][fn][1], ry0 = rv[fp][fn][2], ry1 = rv[fp][fn][3];
-        swap16(rx0, ry0);  // back to the accumulator layout
-        swap16(rx1, ry1);
-        uint32_t yx0 = 0, yx1 = 0, yy0 = 0, yy1 = 0;
-        if constexpr ((EF & VE_ACCUM) != 0) {
-          yx0 = yv[fp][fn][0], yx1 = yv[fp][fn][1], yy0 = yv[fp][fn][2], yy1 = yv[fp][fn][3];
-          swap16(yx0, yy0);
-          swap16(yx1, yy1);
-        }
-        uint32_t o1[2][2], o2[2][2];
+        uint32_t rr[2][2], yy[2][2] = {}, o1[2][2], o2[2][2];  // [X|Y][dword]: x, old xs, y and its activated copy
+        unpack16(rv[fp][fn], rr);  // back to the accumulator layout
+        if constexpr ((EF & VE_ACCUM) != 0) unpack16(yv[fp][fn], yy);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int fm = 2 * fp + h;
           const f32x4 b4 = *reinterpret_cast<const f32x4*>(par + C + wm * 64 + fm * 16 + 4 * g4);
-          const uint32_t rr[2] = {h ? ry0 : rx0, h ? ry1 : rx1};
-          const uint32_t yy[2] = {h ? yy0 : yx0, h ? yy1 : yx1};
-          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu, two channels per packed op
+          // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu (res_out, mt_vconv.h), two channels per packed op
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            f32x2 v = f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]} + f32x2{b4[2 * u], b4[2 * u + 1]};
-            v = v + unpk_bf16(rr[u]);
-            if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-            if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
-            o1[h][u] = pk_bf16(v);
-            o2[h][u] = lrelu_pk(o1[h][u], a.slope);  // the stored state's activated copy
+            res_out<EF | VE_RESID>(f32x2{acc[fm][fn][2 * u], acc[fm][fn][2 * u + 1]}, f32x2{b4[2 * u], b4[2 * u + 1]}, rr[h][u],
+                                   yy[h][u], a.div, a.slope, o1[h][u], o2[h][u]);
           }
         }
-        swap16(o1[0][0], o1[1][0]);
-        swap16(o1[0][1], o1[1][1]);
+        const u32x4 y = pack16(o1);
         if constexpr (VP128_BUF) {
           // the utterance's [L][C] output as a buffer: frames past L fall outside it (store dropped), the tile's
           // discarded frames i >= BN get an offset past any range; every lane still stores
           const unsigned vo = i < BN ? (unsigned)(((n0 + i) * C + wm * 64 + fp * 32 + ch16) * 2) : 0x80000000u;
-          buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
-          if constexpr ((EF & VE_DUAL) != 0) {
-            swap16(o2[0][0], o2[1][0]);
-            swap16(o2[0][1], o2[1][1]);
-            buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
-          }
+          buf_store16<SP>(y, yr, vo);
+          if constexpr ((EF & VE_DUAL) != 0) buf_store16<SP>(pack16(o2), y2r, vo);
           continue;
         }
         const bool ok = i < BN && n0 + i < L;
         const size_t o = ((size_t)b * L + n0 + i) * C + wm * 64 + fp * 32 + ch16;
-        *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
-        if constexpr ((EF & VE_DUAL) != 0) {
-          swap16(o2[0][0], o2[1][0]);
-          swap16(o2[0][1], o2[1][1]);
-          *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]};
-        }
+        *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = y;
+        if constexpr ((EF & VE_DUAL) != 0) *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = pack16(o2);
       }
     issued += 2 * FN * ((EF & VE_DUAL) ? 2 : 1);
     VP_TS(9);
@@ -541,60 +448,24 @@ bool vpair128_supported(int k, int d) {
   return k >= 3 && k % 2 == 1 && NF1 - (k - 1) > 0 && NF1 + d * (k - 1) <= XROWS;
 }
 
-static int vp128_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 int launch_vpair128(int ef, const VPairArgs& a, hipStream_t st) {
-  MT_REQUIRE(!(ef & VE_DIV) || div_rn_ok(a.div), "vpair128: VE_DIV divisor %g outside the exactly-checked set (div_rn)", (double)a.div);
   ef &= ~VE_Y2ONLY;  // stores y as well (VE_Y2ONLY is an option, mt_vconv.h)
-  MT_REQUIRE(a.x && a.w1 && a.w2 && a.b1 && a.b2 && a.y && a.zero && a.trash && a.B > 0 && a.L > 0,
-             "vpair128: null argument / empty");
-  MT_REQUIRE(vpair128_supported(a.taps, a.dil), "vpair128: k %d d %d", a.taps, a.dil);
-  MT_REQUIRE(!(ef & VE_DUAL) || a.y2, "vpair128: y2");
-  MT_REQUIRE(a.y != a.x, "vpair128: y must not alias x (neighbour tiles read x's halo)");
-  const int BN = NF1 - (a.taps - 1);
-  const long ntiles = (long)a.B * ((a.L + BN - 1) / BN);
-  MT_REQUIRE(ntiles < (1L << 31), "vpair128: too many tiles");
-  const int G = (int)std::min<long>(ntiles, vp128_cu_count());
-  // probe: the pair is two of the family's convs (SURVEY §8d algorithmic FLOPs and layer-boundary bytes)
-  const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
-  const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
-  probe_begin(PROBE_VCONV, st);
+  if (pair_check("vpair128", ef, a, vpair128_supported(a.taps, a.dil))) return -1;
   // the compile-time K loop for k = 3 (mt_vpair_set_kernels bit VPK_CTK128) when its fixed row staging covers R1
   const bool ct3 = a.taps == 3 && (vpair_kernels() & VPK_CTK128) != 0 && NF1 + 2 * a.dil <= 32 * XPW;
   const bool wt = store_policy() == ST_WT;  // the store policy (mt_common.h)
-  auto go = [&](auto ec) {
-    constexpr int E = decltype(ec)::value;
-    if (ct3) {
-      (void)VpkReg<3, Vp128Sched<E, 3>, E>::reg;
-      if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 3, ST_WT>), dim3(G), dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((vpair128_kernel<E, 3>), dim3(G), dim3(NT), 0, st, a);
-    }
-    else if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 0, ST_WT>), dim3(G), dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((vpair128_kernel<E>), dim3(G), dim3(NT), 0, st, a);
-  };
-  switch (ef) {
-    case 0: go(std::integral_constant<int, 0>{}); break;
-    case VE_ACCUM: go(std::integral_constant<int, VE_ACCUM>{}); break;
-    case VE_ACCUM | VE_DIV: go(std::integral_constant<int, VE_ACCUM | VE_DIV>{}); break;
-    case VE_ACCUM | VE_DIV | VE_DUAL: go(std::integral_constant<int, VE_ACCUM | VE_DIV | VE_DUAL>{}); break;
-    case VE_DIV: go(std::integral_constant<int, VE_DIV>{}); break;
-    case VE_DIV | VE_DUAL: go(std::integral_constant<int, VE_DIV | VE_DUAL>{}); break;
-    default: set_error("vpair128: epilogue %d not compiled in", ef); return -1;
-  }
-  MT_CHECK_HIP(hipGetLastError());
-  probe_end(PROBE_VCONV, st, flops, bytes, PROBE_TAG_VPAIR128);
-  const int rec[VCLOG_FIELDS] = {ef | 0x10000, C, BN, 0, (int)ntiles, G, a.taps, C, C, a.B, a.L};
-  vclog_record(rec);
-  return 0;
+  return pair_launch("vpair128", C, NF1 - (a.taps - 1), ef, a, st, PROBE_TAG_VPAIR128, [&](int G) {
+    return pair_with_ef(ef, [&](auto ec) {
+      constexpr int E = decltype(ec)::value;
+      if (ct3) {
+        (void)VpkReg<3, Vp128Sched<E, 3>, E>::reg;
+        if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 3, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+        else hipLaunchKernelGGL((vpair128_kernel<E, 3>), dim3(G), dim3(NT), 0, st, a);
+      }
+      else if (wt) hipLaunchKernelGGL((vpair128_kernel<E, 0, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((vpair128_kernel<E>), dim3(G), dim3(NT), 0, st, a);
+    });
+  });
 }
 
 VP_TS_BINDER(vpair128_ts_bind)

@@ -58,32 +58,6 @@ __device__ __forceinline__ int swz(int r) { return (r >> 1) & 2; }
 #define VP32_BUF 1  // 1: row staging and the y / y2 stores through buffer resources (mt_rbconv's RB_BUF)
 #endif
 
-__device__ __forceinline__ void glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-__device__ __forceinline__ void wait_vmcnt(int n) {
-  if (n < 7) {
-    if (n < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (n < 4) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  } else if (n < 15) {
-    if (n < 10) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  } else {
-    if (n < 23) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-    else if (n < 31) asm volatile("s_waitcnt vmcnt(23)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(31)" ::: "memory");
-  }
-}
-
-__device__ __forceinline__ void barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 }  // namespace
 
 template <int EF, int SP = ST_PLAIN>  // SP: the y / y2 stores' policy (mt_common.h); the VE_POST waveform stays plain
@@ -95,25 +69,10 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
   const int g4 = lane >> 4, l16 = lane & 15, lrow = lane >> 2, lp = lane & 3;
   const int k = a.taps, d = a.dil, L = a.L;
   const int h1 = d * (k - 1) / 2, h2 = (k - 1) / 2;
-  const int ntn = (L + BN - 1) / BN;
-  // ragged batch: the live tiles of each utterance (mt_ragged.h)
-  const bool rag = a.lens != nullptr;
-  int* rtc = reinterpret_cast<int*>(smem + RAG_OFF);
-  int* rlv = rtc + RAG_MAXB;
-  if (rag) {
-    rag_build(rtc, rlv, a.lens, a.lmul, L, 0, L, a.B, BN, tid);
-    __syncthreads();
-  }
-  const int ntiles = __builtin_amdgcn_readfirstlane(rag ? rtc[a.B - 1] : a.B * ntn);  // scalar: so is the tile walk
-  const int G = gridDim.x, g = blockIdx.x;
-  const int gl = (G % 8 == 0) ? (g % 8) * (G / 8) + g / 8 : g;
-  const int nmine = gl < ntiles ? (ntiles - gl + G - 1) / G : 0;
-  if (nmine == 0) return;
-  for (int i = tid; i < C; i += NT) {
-    reinterpret_cast<float*>(smem + PAR_OFF)[i] = a.b1[i];
-    reinterpret_cast<float*>(smem + PAR_OFF)[C + i] = a.b2[i];
-  }
-  __syncthreads();
+  PairWalk tiles;
+  if (!tiles.init(a, smem + RAG_OFF, BN, tid)) return;
+  const int nmine = tiles.nmine;
+  pair_load_bias<C, NT>(reinterpret_cast<float*>(smem + PAR_OFF), a, tid);
 
   // VE_POST (the vocoder's last pair): conv2's outputs are frames n0 - PS + i (PS = 3: the 3-frame halo conv_post
   // reads on each side of the tile's BN outputs lies inside the frames conv2 computes validly, i < NF1 - 2 h2 - ... );
@@ -122,16 +81,6 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
   constexpr int PS = POST ? 3 : 0;
   static_assert(!POST || ((EF & VE_ACCUM) && (EF & VE_DIV) && !(EF & VE_DUAL)), "VE_POST: the stage's final xs");
   int issued = 0, xmk = 0;
-  RagWalk walk;
-  auto tile_of = [&](int ti) __attribute__((always_inline)) {  // (utterance, first frame, valid frames) of tile ti
-    const int tile = __builtin_amdgcn_readfirstlane(gl + ti * G);
-    if (rag) return walk.at(rtc, rlv, a.B, BN, tile);
-    RagTile t;
-    t.b = tile / ntn;
-    t.n0 = (tile - t.b * ntn) * BN;
-    t.lv = L;
-    return t;
-  };
   RagTile nxt;  // the tile stage_x staged last (the next tile of the loop)
   // every tap of both convs from the generic packing [32 rows][k][32]: DMA j moves tap (j / 2) % k of conv
   // j / 2k, rows (j & 1) * 16 .. + 15
@@ -148,7 +97,7 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
   // at a multiple of 16 rows, so swz(row) = swz(lrow))
   const int xlane = lrow * RB + ((lp ^ swz(lrow)) * 16);
   auto stage_x = [&](int ti) __attribute__((always_inline)) {
-    nxt = tile_of(ti);
+    nxt = tiles.at(ti);
     if constexpr (VP32_BUF) {
       // the utterance as a buffer of its lv valid frames (past the workgroup's last tile: an empty one, zero rows):
       // row r = frame f0 + r at byte offset (f0 + r) * RB; negative offsets wrap past num_records, so the range
@@ -182,12 +131,6 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
     }
     issued += XROWS / 128;
     xmk = issued;
-  };
-
-  auto swap16 = [](uint32_t& x, uint32_t& y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
-    x = r[0];
-    y = r[1];
   };
 
   f32x4 acc[2][FN];
@@ -252,7 +195,7 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
     VP_TS(10);
     wait_vmcnt(issued - xmk);
     VP_TS(0);
-    barrier();
+    lds_barrier();
     VP_TS(1);
     u32x4 rv[FN], yv[FN];  // residual x and (VE_ACCUM) old xs of this lane's outputs
 #pragma unroll
@@ -260,7 +203,7 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
       const int r = wave * WNC + fn * 16 + l16 + HALO2 + h1 - PS;
       rv[fn] = *reinterpret_cast<const u32x4*>(smem + r * RB + ((qc ^ swz(r)) * 16));
     }
-    barrier();
+    lds_barrier();
     VP_TS(2);
 #pragma unroll
     for (int i = 0; i < XBUF / 16 / NT; ++i) {
@@ -270,7 +213,7 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
       for (int w = 0; w < 4; ++w) v[w] = lrelu_pk(v[w], a.slope);
       *reinterpret_cast<u32x4*>(smem + e * 16) = v;
     }
-    barrier();  // activated rows published
+    lds_barrier();  // activated rows published
     VP_TS(3);
     // ---- 2. conv1 ----
     int ymk = 0;
@@ -305,13 +248,11 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
         o[h][0] = ok ? lrelu_pk_f(f32x2{acc[h][fn][0], acc[h][fn][1]} + f32x2{b4[0], b4[1]}, a.slope) : 0u;
         o[h][1] = ok ? lrelu_pk_f(f32x2{acc[h][fn][2], acc[h][fn][3]} + f32x2{b4[2], b4[3]}, a.slope) : 0u;
       }
-      swap16(o[0][0], o[1][0]);
-      swap16(o[0][1], o[1][1]);
-      *reinterpret_cast<u32x4*>(smem + T_OFF + j * RB + ((qc ^ swz(j)) * 16)) = u32x4{o[0][0], o[0][1], o[1][0], o[1][1]};
+      *reinterpret_cast<u32x4*>(smem + T_OFF + j * RB + ((qc ^ swz(j)) * 16)) = pack16(o);
     }
     VP_TS(5);
     // ---- 3. conv2 ----
-    barrier();  // T published; every wave is past conv1's reads of the row buffer: stage the next tile's rows
+    lds_barrier();  // T published; every wave is past conv1's reads of the row buffer: stage the next tile's rows
     stage_x(ti + 1);
     VP_TS(6);
     conv(1, smem + T_OFF, wave * WNC + l16 + HALO2 - h2 - PS, 1);
@@ -328,46 +269,32 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
     const auto yr = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)bu * L * C, (short)0, (int)((unsigned)L * RB), 0x00020000);
     const auto y2r = __builtin_amdgcn_make_buffer_rsrc(((EF & VE_DUAL) ? a.y2 : a.y) + (size_t)bu * L * C, (short)0,
                                                        (int)((unsigned)L * RB), 0x00020000);
-    if constexpr (POST) barrier();  // every wave is past conv2's reads of T: xs replaces it as conv_post's input
+    if constexpr (POST) lds_barrier();  // every wave is past conv2's reads of T: xs replaces it as conv_post's input
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) {
       const int i = wave * WNC + fn * 16 + l16;  // output frame n0 - PS + i
-      uint32_t rx0 = rv[fn][0], rx1 = rv[fn][1], ry0 = rv[fn][2], ry1 = rv[fn][3];
-      swap16(rx0, ry0);  // back to the accumulator layout
-      swap16(rx1, ry1);
-      uint32_t yx0 = 0, yx1 = 0, yy0 = 0, yy1 = 0;
-      if constexpr ((EF & VE_ACCUM) != 0) {
-        yx0 = yv[fn][0], yx1 = yv[fn][1], yy0 = yv[fn][2], yy1 = yv[fn][3];
-        swap16(yx0, yy0);
-        swap16(yx1, yy1);
-      }
-      uint32_t o1[2][2], o2[2][2];
+      uint32_t rr[2][2], yy[2][2] = {}, o1[2][2], o2[2][2];  // [X|Y][dword]: x, old xs, y and its activated copy
+      unpack16(rv[fn], rr);  // back to the accumulator layout
+      if constexpr ((EF & VE_ACCUM) != 0) unpack16(yv[fn], yy);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(par + C + h * 16 + 4 * g4);
-        const uint32_t rr[2] = {h ? ry0 : rx0, h ? ry1 : rx1};
-        const uint32_t yy[2] = {h ? yy0 : yx0, h ? yy1 : yx1};
-        // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu, two channels per packed op
+        // round(acc + b2 + x [+ xs] [/ nk]) and its lrelu (res_out, mt_vconv.h), two channels per packed op
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          f32x2 v = f32x2{acc[h][fn][2 * u], acc[h][fn][2 * u + 1]} + f32x2{b4[2 * u], b4[2 * u + 1]};
-          v = v + unpk_bf16(rr[u]);
-          if constexpr ((EF & VE_ACCUM) != 0) v = unpk_bf16(yy[u]) + v;
-          if constexpr ((EF & VE_DIV) != 0) v = f32x2{div_rn(v.x, a.div, 1.f / a.div), div_rn(v.y, a.div, 1.f / a.div)};
-          o1[h][u] = pk_bf16(v);
-          o2[h][u] = lrelu_pk(o1[h][u], a.slope);  // the stored state's activated copy
+          res_out<EF | VE_RESID>(f32x2{acc[h][fn][2 * u], acc[h][fn][2 * u + 1]}, f32x2{b4[2 * u], b4[2 * u + 1]}, rr[h][u],
+                                 yy[h][u], a.div, a.slope, o1[h][u], o2[h][u]);
         }
       }
-      swap16(o1[0][0], o1[1][0]);
-      swap16(o1[0][1], o1[1][1]);
+      const u32x4 y = pack16(o1);
       if constexpr (POST) {
         // conv_post's input v = bf16(lrelu(xs, 0.01)) of frame n0 - 3 + i into T row i (zero outside the utterance:
         // conv_post's zero padding), the layout post_taps reads
         const int f = n0 - PS + i;
         const bool in = f >= 0 && f < Lt;
         u32x4 v = {0u, 0u, 0u, 0u};
-        if (in) v = u32x4{lrelu_pk(o1[0][0], a.post_slope), lrelu_pk(o1[0][1], a.post_slope),
-                          lrelu_pk(o1[1][0], a.post_slope), lrelu_pk(o1[1][1], a.post_slope)};
+        if (in) v = u32x4{lrelu_pk(y[0], a.post_slope), lrelu_pk(y[1], a.post_slope), lrelu_pk(y[2], a.post_slope),
+                          lrelu_pk(y[3], a.post_slope)};
         *reinterpret_cast<u32x4*>(smem + T_OFF + i * RB + ((qc ^ swz(i)) * 16)) = v;
         continue;
       }
@@ -377,27 +304,19 @@ __global__ __launch_bounds__(NT) void vpair32_kernel(VPairArgs a) {
         // the issue counts are unchanged)
         const bool keep = !(fn == FN - 1 && wave == 7);
         const unsigned vo = keep ? (unsigned)(((n0 + i) * C + ch16) * 2) : 0x80000000u;
-        buf_store16<SP>(u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]}, yr, vo);
-        if constexpr ((EF & VE_DUAL) != 0) {
-          swap16(o2[0][0], o2[1][0]);
-          swap16(o2[0][1], o2[1][1]);
-          buf_store16<SP>(u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]}, y2r, vo);
-        }
+        buf_store16<SP>(y, yr, vo);
+        if constexpr ((EF & VE_DUAL) != 0) buf_store16<SP>(pack16(o2), y2r, vo);
         continue;
       }
       const bool ok = i < BN && n0 + i < L;
       const size_t o = ((size_t)b * L + n0 + i) * C + ch16;
-      *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = u32x4{o1[0][0], o1[0][1], o1[1][0], o1[1][1]};
-      if constexpr ((EF & VE_DUAL) != 0) {
-        swap16(o2[0][0], o2[1][0]);
-        swap16(o2[0][1], o2[1][1]);
-        *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = u32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]};
-      }
+      *reinterpret_cast<u32x4*>(ok ? a.y + o : a.trash + 8 * lane) = y;
+      if constexpr ((EF & VE_DUAL) != 0) *reinterpret_cast<u32x4*>(ok ? a.y2 + o : a.trash + 8 * lane) = pack16(o2);
     }
     if constexpr (POST) {
       // conv_post of the tile's BN frames (post_taps / post_combine: 6 blocks of 16 per wave), tanh(. + bias), the
       // waveform stored (frames past the utterance: 0, as post_conv_kernel; past L or BN: dropped by the range check)
-      barrier();
+      lds_barrier();
       const float* wbase = a.wav + (size_t)bu * L;
       const auto wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), (short)0, (int)((unsigned)L * 4), 0x00020000);
       // conv_post's A operand fetched here (cache-resident) rather than held through the tile loop (VGPR pressure)
@@ -442,57 +361,23 @@ bool vpair32_supported(int k, int d) {
   return k >= 3 && k % 2 == 1 && k <= KMAX && (k - 1) / 2 <= HALO2 && NF1 + d * (k - 1) <= XROWS;
 }
 
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 int launch_vpair32(int ef, const VPairArgs& a, hipStream_t st) {
-  MT_REQUIRE(!(ef & VE_DIV) || div_rn_ok(a.div), "vpair32: VE_DIV divisor %g outside the exactly-checked set (div_rn)", (double)a.div);
   ef &= ~VE_Y2ONLY;  // stores y as well (VE_Y2ONLY is an option, mt_vconv.h)
-  MT_REQUIRE(a.x && a.w1 && a.w2 && a.b1 && a.b2 && a.y && a.zero && a.trash && a.B > 0 && a.L > 0,
-             "vpair32: null argument / empty");
-  MT_REQUIRE(vpair32_supported(a.taps, a.dil) && a.taps % 2 == 1, "vpair32: k %d d %d", a.taps, a.dil);
-  MT_REQUIRE(!(ef & VE_DUAL) || a.y2, "vpair32: y2");
+  if (pair_check("vpair32", ef, a, vpair32_supported(a.taps, a.dil) && a.taps % 2 == 1)) return -1;
   MT_REQUIRE(!(ef & VE_POST) || (a.post_w && a.post_b && a.wav && (ef & ~VE_POST) == (VE_ACCUM | VE_DIV) &&
                                  (a.taps - 1) / 2 + 3 <= HALO2),
              "vpair32: VE_POST needs conv_post's weights, bias and the waveform, the stage's final (ACCUM | DIV) pair "
              "and k <= %d", 2 * (HALO2 - 3) + 1);
-  MT_REQUIRE(a.y != a.x, "vpair32: y must not alias x (neighbour tiles read x's halo)");
-  const long ntiles = (long)a.B * ((a.L + BN - 1) / BN);
-  const int G = (int)std::min<long>(ntiles, cu_count());
-  const double flops = 2.0 * 2.0 * C * C * a.taps * (double)a.B * a.L;
-  const double bytes = 2.0 * (2.0 * 2.0 * C * (double)a.B * a.L) + 2.0 * 2.0 * C * C * a.taps;
-  probe_begin(PROBE_VCONV, st);
   const bool wt = store_policy() == ST_WT;  // the store policy (mt_common.h)
-#define MT_VP32(E)                                                                                 \
-  if (wt) hipLaunchKernelGGL((vpair32_kernel<(E), ST_WT>), dim3(G), dim3(NT), 0, st, a);           \
-  else hipLaunchKernelGGL((vpair32_kernel<(E)>), dim3(G), dim3(NT), 0, st, a);                     \
-  break
-  switch (ef) {
-    case 0: MT_VP32(0);
-    case VE_ACCUM: MT_VP32(VE_ACCUM);
-    case VE_ACCUM | VE_DIV: MT_VP32(VE_ACCUM | VE_DIV);
-    case VE_ACCUM | VE_DIV | VE_DUAL: MT_VP32(VE_ACCUM | VE_DIV | VE_DUAL);
-    case VE_DIV: MT_VP32(VE_DIV);
-    case VE_DIV | VE_DUAL: MT_VP32(VE_DIV | VE_DUAL);
-#undef MT_VP32
-    case VE_ACCUM | VE_DIV | VE_POST:  // 4-byte waveform stores only: plain under every policy
-      hipLaunchKernelGGL((vpair32_kernel<VE_ACCUM | VE_DIV | VE_POST>), dim3(G), dim3(NT), 0, st, a);
-      break;
-    default: set_error("vpair32: epilogue %d not compiled in", ef); return -1;
-  }
-  MT_CHECK_HIP(hipGetLastError());
-  probe_end(PROBE_VCONV, st, flops, bytes, PROBE_TAG_VPAIR32);
-  const int rec[VCLOG_FIELDS] = {ef | 0x10000, C, BN, 0, (int)ntiles, G, a.taps, C, C, a.B, a.L};
-  vclog_record(rec);
-  return 0;
+  return pair_launch("vpair32", C, BN, ef, a, st, PROBE_TAG_VPAIR32, [&](int G) {
+    return pair_with_ef<VE_POST>(ef, [&](auto ec) {
+      constexpr int E = decltype(ec)::value;
+      if constexpr ((E & VE_POST) != 0)  // 4-byte waveform stores only: plain under every policy
+        hipLaunchKernelGGL((vpair32_kernel<E>), dim3(G), dim3(NT), 0, st, a);
+      else if (wt) hipLaunchKernelGGL((vpair32_kernel<E, ST_WT>), dim3(G), dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((vpair32_kernel<E>), dim3(G), dim3(NT), 0, st, a);
+    });
+  });
 }
 
 VP_TS_BINDER(vpair32_ts_bind)

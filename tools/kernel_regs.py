@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register allocation of two builds of libmatcha_hip.so, kernel by kernel, from the gfx950 code object's metadata
-(.sgpr_count, .vgpr_count, .sgpr_spill_count, .vgpr_spill_count, .private_segment_fixed_size = scratch bytes per lane).
+(.sgpr_count, .vgpr_count, .sgpr_spill_count, .vgpr_spill_count, .private_segment_fixed_size = scratch bytes per lane,
+.group_segment_fixed_size = LDS bytes per workgroup).
 Kernels are matched by demangled name; a template argument list the newer build extended with trailing defaulted
 arguments (..., 0>) matches its shorter form. Prints every kernel whose figures differ, the kernels only one build
 has (with their spills), and a summary. CPU only.
@@ -13,51 +14,68 @@ import tempfile
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 LLVM = os.path.join(ROCM, "llvm", "bin")
-FIELDS = (".sgpr_count", ".vgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size")
+FIELDS = (".sgpr_count", ".vgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size",
+          ".group_segment_fixed_size")
 
 
-def kernels(so):
+def code_objects(so, td):
+    """Writes the gfx950 code objects of library `so` into directory td; -> their paths (tools/isa_diff.py too)."""
     # the library's .hip_fatbin section holds one uncompressed offload bundle per translation unit: magic, entry count,
     # then (offset, size, triple length, triple) per entry
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    notes = ""
-    with tempfile.TemporaryDirectory() as td:
-        fb = os.path.join(td, "fatbin")
-        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", so, fb],
-                       check=True)
-        blob = open(fb, "rb").read()
-        pos, n = blob.find(magic), 0
-        assert pos >= 0, f"{so}: no uncompressed offload bundle in .hip_fatbin"
-        while pos >= 0:
-            cnt = int.from_bytes(blob[pos + 24:pos + 32], "little")
-            p = pos + 32
-            for _ in range(cnt):
-                off, size, tl = (int.from_bytes(blob[p + 8 * i:p + 8 * i + 8], "little") for i in range(3))
-                triple = blob[p + 24:p + 24 + tl].decode()
-                p += 24 + tl
-                if "gfx950" in triple and size:
-                    co = os.path.join(td, f"co{n}")
-                    n += 1
-                    open(co, "wb").write(blob[pos + off:pos + off + size])
-                    notes += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True,
-                                            capture_output=True, text=True).stdout
-            pos = blob.find(magic, pos + 24)
-    out, cur = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*-?\s*(\.[a-z_]+):\s*(.*)$", line)
-        if not m:
-            continue
-        k, v = m.group(1), m.group(2).strip()
-        if k == ".name":
-            cur = {}
-            out[v.strip("'\"")] = cur
-        elif cur is not None and k in FIELDS:
-            cur[k] = int(v)
-    names = list(out)
+    fb = os.path.join(td, "fatbin")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", so, fb], check=True)
+    blob = open(fb, "rb").read()
+    pos, cos = blob.find(magic), []
+    assert pos >= 0, f"{so}: no uncompressed offload bundle in .hip_fatbin"
+    while pos >= 0:
+        cnt = int.from_bytes(blob[pos + 24:pos + 32], "little")
+        p = pos + 32
+        for _ in range(cnt):
+            off, size, tl = (int.from_bytes(blob[p + 8 * i:p + 8 * i + 8], "little") for i in range(3))
+            triple = blob[p + 24:p + 24 + tl].decode()
+            p += 24 + tl
+            if "gfx950" in triple and size:
+                cos.append(os.path.join(td, f"co{len(cos)}"))
+                open(cos[-1], "wb").write(blob[pos + off:pos + off + size])
+        pos = blob.find(magic, pos + 24)
+    return cos
+
+
+def demangle(names):
     filt = os.path.join(LLVM, "llvm-cxxfilt")
-    dem = subprocess.run([filt if os.path.exists(filt) else "c++filt"], input="\n".join(names), capture_output=True, text=True,
-                         check=True).stdout.splitlines()
-    return {d: out[n] for n, d in zip(names, dem) if out[n]}
+    return subprocess.run([filt if os.path.exists(filt) else "c++filt"], input="\n".join(names), capture_output=True,
+                          text=True, check=True).stdout.splitlines()
+
+
+def kernels(so):
+    with tempfile.TemporaryDirectory() as td:
+        notes = "".join(subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True,
+                                       capture_output=True, text=True).stdout for co in code_objects(so, td))
+    # amdhsa.kernels is a list of maps with sorted keys: a record starts at a "- " item of the list's own indentation
+    # (its .args items sit deeper), and its fields come before as well as after its .name
+    out, rec, ind = {}, None, None
+    for line in notes.splitlines():
+        if "amdhsa.kernels:" in line:
+            ind = -1
+            continue
+        m = re.match(r"(\s*)(- )?(\.[a-z_]+):\s*(.*)$", line)
+        if not m or ind is None:
+            if not m and not line.startswith(" "):  # the list has ended
+                ind = None
+            continue
+        col = len(m.group(1))
+        if m.group(2) and ind in (-1, col):
+            ind, rec = col, {}
+        if rec is None or col + (2 if m.group(2) else 0) != ind + 2:
+            continue
+        k, v = m.group(3), m.group(4).strip()
+        if k == ".name":
+            out[v.strip("'\"")] = rec
+        elif k in FIELDS:
+            rec[k] = int(v)
+    names = list(out)
+    return {d: out[n] for n, d in zip(names, demangle(names)) if out[n]}
 
 
 def shorten(name):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch times of the vocoder's fused-pair / per-layer ResBlock launches (launch probe, PROBE_VCONV) at one
 batch shape, grouped by kernel kind and kernel size k (from the probe's FLOP count), after a warm-up call.
-Env knobs are read by the library (e.g. MT_VPAIR3); PAIR sets the vocoder pair mode. Usage: python tools/pair_probe.py [B] [T] [reps]"""
+Env knobs are read by the library (e.g. MT_VPAIR3=0: the k = 3 pairs on the ring kernel); PAIR sets the vocoder pair mode. Usage: python tools/pair_probe.py [B] [T] [reps]"""
 import os
 import sys
 from collections import defaultdict
