@@ -18,6 +18,9 @@
  *                                   MOS_audiou_generator.ipynb:265-277) for a whole padded batch in one launch chain
  *   mt_resample, mt_audio_stats, <- the host steps after the vocoder, main.py:198-201 (`.clamp(-1, 1)`, soundfile's
  *   mt_audio_encode                 PCM16 write), plus rate conversion and level, which the reference leaves to callers
+ *   mt_window_gather,            <- streaming delivery of the steps above (windows of the mel / the audio, the outputs
+ *   mt_window_scatter,              that became final): no counterpart in the reference, which vocodes whole utterances
+ *   mt_resample_range
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
  *   mt_durations_tokens, mt_align   duration control and a forced aligner for inference: no counterpart in the
  *                                   reference (its log-prior train_standalone.py:639-644 in direct form, textbook MAS)
@@ -355,6 +358,16 @@ int mt_stft_magnitude(const float* audio, int B, int L, float* mag, void* stream
 size_t mt_resample_workspace_bytes(int half, int up, int down);
 int mt_resample(const float* audio, int B, int L, const int32_t* lens, int lmul, const float* taps_polyphase, int half,
                 int up, int down, float* out, int Lout, int32_t* out_lens, void* ws, size_t ws_bytes, void* stream);
+/* The outputs [m_lo, m_lo + cnt) of mt_resample's rows, without the others: out[b][j] (fp32 [B][cnt]) has the bits of
+ * mt_resample's out[b][m_lo + j] while m_lo + j < ceil(len_b up / down) and is zero past it; out_cnt[b] (int32 [B]) =
+ * that row's count of such j, clamp(ceil(len_b up / down) - m_lo, 0, cnt). Same chain, same table re-order, phase and
+ * input span taken from the output's index m_lo + j in the utterance. Of audio[b] it reads only the samples between
+ * the first and the last one the chains of the requested outputs touch, the last being
+ * (half + (m_lo + out_cnt[b] - 1) down) / up: later samples of the row need not be written yet (streaming delivery,
+ * DESIGN.md §20). m_lo >= 0, cnt >= 1, m_lo + cnt < 2^31 - 2048. Workspace as mt_resample. */
+int mt_resample_range(const float* audio, int B, int L, const int32_t* lens, int lmul, const float* taps_polyphase,
+                      int half, int up, int down, int m_lo, int cnt, float* out, int32_t* out_cnt, void* ws,
+                      size_t ws_bytes, void* stream);
 /* peak[b] = max |x| (fp32 [B]) and meansq[b] = sum x^2 / len_b (fp64 [B]; 0 for an empty row) over the first len_b =
  * lens[b] samples (int32 [B], device, clamped to [0, L]; NULL: L). The squares are summed in fp64 over tiles of 4096
  * samples counted from the row's start, then the partials in a fixed order: no atomics. */
@@ -369,6 +382,22 @@ int mt_audio_stats(const float* audio, int B, int L, const int32_t* lens, float*
  * place. gain_out fp32 [B], may be NULL. */
 int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const float* peak, const double* meansq,
                     int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Streaming delivery (matcha_hip/stream_plan.py is the specification of the windows): cut one window
+ * per row out of a full-length buffer, and write the part of a processed window that became final back into one.
+ * Plain copies. All tables are int32 [R] in device memory, R <= 512 (one ragged launch chain); an entry that points
+ * outside its buffer (negative, a row index past the batch, a range past the row) is clamped away inside the kernel:
+ * such a gather reads zeros, such a scatter writes nothing, neither touches memory out of range.
+ * ------------------------------------------------------------------------------------- */
+/* rows[r][c][w] = src[row_src[r]][c][row_start[r] + w] for w < row_len[r], else 0. src fp32 [Bs][C][Ls], rows fp32
+ * [R][C][W] (written whole). C = 80 for a mel [B][80][T] (start and len in frames), C = 1 for audio (in samples). */
+int mt_window_gather(const float* src, int Bs, int C, int Ls, const int32_t* row_src, const int32_t* row_start,
+                     const int32_t* row_len, int R, int W, float* rows, void* stream);
+/* dst[row_dst[r]][dst_start[r] + i] = rows[r][crop_from[r] + i] for i < crop_len[r]. rows fp32 [R][W], dst fp32
+ * [Bd][Ld]; the rest of dst keeps its contents. Two rows r must not write the same samples of dst. */
+int mt_window_scatter(const float* rows, int R, int W, const int32_t* row_dst, const int32_t* crop_from,
+                      const int32_t* dst_start, const int32_t* crop_len, float* dst, int Bd, int Ld, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Log-mel featurizer (§8f rank 4), replacing train_standalone.py:164-201 `mel_spectrogram(y, 1024, 80,

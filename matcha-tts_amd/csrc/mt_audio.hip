@@ -14,6 +14,9 @@
 //   LDS: the whole table (<= 52.5 KiB at the rates of a 22,050 Hz source) and the tile's input span, staged with
 //   coalesced loads, zero outside [0, len). When table + span exceed 64 KiB (factors far from the audio rates) the
 //   same chain reads both from global memory instead (STAGED = false): same bits, no LDS.
+//   mt_resample_range runs the same kernel on the outputs [m_lo, m_lo + cnt) of every row (mg0 = m_lo; 0 for
+//   mt_resample): phase, table column and input span come from the output's index in the utterance, so a slice has
+//   the bits of the whole, and a tile reads no sample past the one its last output's chain starts at.
 // audio_stats_kernel: peak = max |x| and the fp64 sum of x^2 over tiles of ST_TILE samples counted from the
 //   utterance's start, then audio_stats_final_kernel sums the partials of one utterance in a fixed order. No atomics.
 // audio_encode_kernel: gain from the stats (fp64, rounded to fp32), v = clamp(g x, -1, 1) in fp32, then f32 / PCM16
@@ -54,20 +57,24 @@ template <bool STAGED>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __restrict__ audio, int L,
                                                               const int* __restrict__ lens, int lmul,
                                                               const float* __restrict__ tab, int tabN, int half,
-                                                              int up, int down, int Q, int r0,
+                                                              int up, int down, int Q, int r0, int mg0,
                                                               float* __restrict__ out, int Lout,
                                                               int* __restrict__ out_lens) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.y, tid = threadIdx.x;
-  const int m0 = blockIdx.x * RS_TN;
+  // the row holds the outputs [mg0, mg0 + Lout) of the utterance (mt_resample: mg0 = 0, the whole utterance;
+  // mt_resample_range: a slice of it). m0 and everything derived from it (phase, input span) count from output 0.
+  const int t0 = blockIdx.x * RS_TN;
+  const int m0 = mg0 + t0;
   const int len = utt_len(lens, b, lmul, L);
   const long long no = ((long long)len * up + down - 1) / down;
-  const int n_out = (int)(no < Lout ? no : Lout);
-  if (blockIdx.x == 0 && tid == 0) out_lens[b] = n_out;
-  float* y = out + (size_t)b * Lout;
-  const int nrow = min(RS_TN, Lout - m0);  // outputs of this tile inside the row
+  const long long lend = (long long)mg0 + Lout;
+  const int n_out = (int)(no < lend ? no : lend);
+  if (blockIdx.x == 0 && tid == 0) out_lens[b] = max(n_out - mg0, 0);
+  float* y = out + (size_t)b * Lout + t0;  // y[j]: output m0 + j
+  const int nrow = min(RS_TN, Lout - t0);  // outputs of this tile inside the row
   if (m0 >= n_out) {
-    for (int j = tid; j < nrow; j += RS_THREADS) y[m0 + j] = 0.f;
+    for (int j = tid; j < nrow; j += RS_THREADS) y[j] = 0.f;
     return;
   }
   const int nt = min(RS_TN, n_out - m0);   // ... and inside the utterance
@@ -109,7 +116,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
 #pragma unroll
       for (int u = 0; u < RS_U; ++u) {
         const int j = j0 + u * RS_THREADS;
-        if (j < nrow) y[m0 + j] = j < nt ? acc[u] : 0.f;
+        if (j < nrow) y[j] = j < nt ? acc[u] : 0.f;
       }
     }
   } else {
@@ -124,7 +131,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
           acc = __builtin_fmaf(tab[(size_t)q * up + r], xv, acc);
         }
       }
-      y[m0 + j] = acc;
+      y[j] = acc;
     }
   }
 }
@@ -293,16 +300,10 @@ size_t resample_workspace_bytes(int half, int up, int down) {
   return table_floats(half, up) * sizeof(float);
 }
 
-int resample(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
-             int down, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (resample_check(half, up, down) != 0) return -1;
-  MT_REQUIRE(B > 0 && B <= AU_MAXB && L > 0, "resample: B %d (1..%d), L %d", B, AU_MAXB, L);
-  const long long need = ((long long)L * up + down - 1) / down;
-  MT_REQUIRE(need < (1ll << 31) - RS_TN, "resample: %lld output samples per row", need);
-  MT_REQUIRE(Lout >= need, "resample: Lout %d < ceil(L up / down) = %lld", Lout, need);
-  MT_REQUIRE(Lout < (1ll << 31) - RS_TN, "resample: Lout %d", Lout);
-  MT_REQUIRE(!lens || lmul > 0, "resample: length multiplier %d", lmul);
-  MT_REQUIRE(audio && taps && out && out_lens, "resample: null argument");
+// the table re-order, then resample_kernel on the outputs [mg0, mg0 + Lout) of every row (the callers check the rest)
+static int resample_launch(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half,
+                           int up, int down, int mg0, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes,
+                           hipStream_t st) {
   const size_t tabN = table_floats(half, up);
   MT_REQUIRE(ws && ws_bytes >= tabN * sizeof(float) && ((uintptr_t)ws & 15) == 0,
              "resample: workspace too small or not 16-byte aligned");
@@ -318,12 +319,36 @@ int resample(const float* audio, int B, int L, const int* lens, int lmul, const 
   const dim3 grid((Lout + RS_TN - 1) / RS_TN, B);
   if (lds <= (size_t)RS_LDS_MAX)
     hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(RS_THREADS), lds, st, audio, L, lens, lmul, tab, (int)tabN,
-                       half, up, down, Q, r0, out, Lout, out_lens);
+                       half, up, down, Q, r0, mg0, out, Lout, out_lens);
   else
     hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(RS_THREADS), 0, st, audio, L, lens, lmul, tab, (int)tabN,
-                       half, up, down, Q, r0, out, Lout, out_lens);
+                       half, up, down, Q, r0, mg0, out, Lout, out_lens);
   MT_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+int resample(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
+             int down, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (resample_check(half, up, down) != 0) return -1;
+  MT_REQUIRE(B > 0 && B <= AU_MAXB && L > 0, "resample: B %d (1..%d), L %d", B, AU_MAXB, L);
+  const long long need = ((long long)L * up + down - 1) / down;
+  MT_REQUIRE(need < (1ll << 31) - RS_TN, "resample: %lld output samples per row", need);
+  MT_REQUIRE(Lout >= need, "resample: Lout %d < ceil(L up / down) = %lld", Lout, need);
+  MT_REQUIRE(Lout < (1ll << 31) - RS_TN, "resample: Lout %d", Lout);
+  MT_REQUIRE(!lens || lmul > 0, "resample: length multiplier %d", lmul);
+  MT_REQUIRE(audio && taps && out && out_lens, "resample: null argument");
+  return resample_launch(audio, B, L, lens, lmul, taps, half, up, down, 0, out, Lout, out_lens, ws, ws_bytes, st);
+}
+
+int resample_range(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
+                   int down, int m_lo, int cnt, float* out, int* out_cnt, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (resample_check(half, up, down) != 0) return -1;
+  MT_REQUIRE(B > 0 && B <= AU_MAXB && L > 0, "resample_range: B %d (1..%d), L %d", B, AU_MAXB, L);
+  MT_REQUIRE(m_lo >= 0 && cnt > 0, "resample_range: outputs [%d, %d + %d)", m_lo, m_lo, cnt);
+  MT_REQUIRE((long long)m_lo + cnt < (1ll << 31) - RS_TN, "resample_range: outputs [%d, %d + %d)", m_lo, m_lo, cnt);
+  MT_REQUIRE(!lens || lmul > 0, "resample_range: length multiplier %d", lmul);
+  MT_REQUIRE(audio && taps && out && out_cnt, "resample_range: null argument");
+  return resample_launch(audio, B, L, lens, lmul, taps, half, up, down, m_lo, out, cnt, out_cnt, ws, ws_bytes, st);
 }
 
 size_t audio_stats_workspace_bytes(int B, int L) {

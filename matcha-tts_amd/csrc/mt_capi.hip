@@ -27,11 +27,18 @@ int log_mel(const float* audio, int B, int L, const float* basis, float mean, fl
 size_t resample_workspace_bytes(int half, int up, int down);
 int resample(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
              int down, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes, hipStream_t st);
+int resample_range(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half, int up,
+                   int down, int m_lo, int cnt, float* out, int* out_cnt, void* ws, size_t ws_bytes, hipStream_t st);
 size_t audio_stats_workspace_bytes(int B, int L);
 int audio_stats(const float* audio, int B, int L, const int* lens, float* peak, double* meansq, void* ws,
                 size_t ws_bytes, hipStream_t st);
 int audio_encode(const float* audio, int B, int L, const int* lens, const float* peak, const double* meansq,
                  int normalize, double level, int limit, int encoding, void* out, float* gain_out, hipStream_t st);
+// mt_stream.hip
+int window_gather(const float* src, int Bs, int C, int Ls, const int* row_src, const int* row_start,
+                  const int* row_len, int R, int W, float* rows, hipStream_t st);
+int window_scatter(const float* rows, int R, int W, const int* row_dst, const int* crop_from, const int* dst_start,
+                   const int* crop_len, float* dst, int Bd, int Ld, hipStream_t st);
 }  // namespace mt
 
 struct mt_encoder {
@@ -430,6 +437,12 @@ int mt_resample(const float* audio, int B, int L, const int32_t* lens, int lmul,
   return mt::resample(audio, B, L, lens, lmul, taps_polyphase, half, up, down, out, Lout, out_lens, ws, ws_bytes,
                       (hipStream_t)stream);
 }
+int mt_resample_range(const float* audio, int B, int L, const int32_t* lens, int lmul, const float* taps_polyphase,
+                      int half, int up, int down, int m_lo, int cnt, float* out, int32_t* out_cnt, void* ws,
+                      size_t ws_bytes, void* stream) {
+  return mt::resample_range(audio, B, L, lens, lmul, taps_polyphase, half, up, down, m_lo, cnt, out, out_cnt, ws,
+                            ws_bytes, (hipStream_t)stream);
+}
 size_t mt_audio_stats_workspace_bytes(int B, int L) { return mt::audio_stats_workspace_bytes(B, L); }
 int mt_audio_stats(const float* audio, int B, int L, const int32_t* lens, float* peak, double* meansq, void* ws,
                    size_t ws_bytes, void* stream) {
@@ -439,6 +452,16 @@ int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const
                     int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream) {
   return mt::audio_encode(audio, B, L, lens, peak, meansq, normalize, level, limit, encoding, out, gain_out,
                           (hipStream_t)stream);
+}
+
+// ---- streaming delivery: window gather / scatter ----
+int mt_window_gather(const float* src, int Bs, int C, int Ls, const int32_t* row_src, const int32_t* row_start,
+                     const int32_t* row_len, int R, int W, float* rows, void* stream) {
+  return mt::window_gather(src, Bs, C, Ls, row_src, row_start, row_len, R, W, rows, (hipStream_t)stream);
+}
+int mt_window_scatter(const float* rows, int R, int W, const int32_t* row_dst, const int32_t* crop_from,
+                      const int32_t* dst_start, const int32_t* crop_len, float* dst, int Bd, int Ld, void* stream) {
+  return mt::window_scatter(rows, R, W, row_dst, crop_from, dst_start, crop_len, dst, Bd, Ld, (hipStream_t)stream);
 }
 
 size_t mt_maximum_path_workspace_bytes(int B, int Tx, int Ty) { return mt::mas_workspace_bytes(B, Tx, Ty); }

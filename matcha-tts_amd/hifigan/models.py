@@ -175,6 +175,12 @@ class Generator(nn.Module):
                     out[b:b + 1, :, :n * hop] = eng.forward(self.packed(x.device), x[b:b + 1, :, :n].contiguous())
             return out
 
+    def receptive_field(self) -> int:
+        """Extension: the mel frames on each side an output sample can depend on, derived from the config
+        (matcha_hip.stream_plan.vocoder_reach; 13 for v1). hifigan.stream.WaveStreamer's halo."""
+        from matcha_hip import stream_plan
+        return stream_plan.vocoder_reach(self.h)
+
     def remove_weight_norm(self):
         print("Removing weight norm...")
         for m in self.ups:

@@ -94,6 +94,10 @@ SIGNATURES = {
     "mt_denoise_ragged": (c_int, [P, c_int, c_int, P, c_int, P, c_float, P, P, c_size_t, P]),
     "mt_resample_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mt_resample": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_size_t, P]),
+    "mt_resample_range": (c_int, [P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t,
+                                  P]),
+    "mt_window_gather": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P]),
+    "mt_window_scatter": (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, c_int, P]),
     "mt_audio_stats_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mt_audio_stats": (c_int, [P, c_int, c_int, P, P, P, P, c_size_t, P]),
     "mt_audio_encode": (c_int, [P, c_int, c_int, P, P, P, c_int, c_double, c_int, c_int, P, P, P]),

@@ -7,6 +7,8 @@ csrc/mt_audio.hip are tested against.
   ``firwin(2 * half + 1, 1 / max(up, down), window=("kaiser", beta)) * up``, without scipy.
 * ``resample_ref``: ``y[m] = sum_k h[half + m * down - k * up] * x[k]`` in fp64, ``ceil(n * up / down)`` outputs:
   zero padding at both ends, zero phase, sample 0 stays at time 0.
+* ``resample_range_ref``: a range of those outputs evaluated alone, the same sum per output (mt_resample_range, the
+  streaming resampler of DESIGN.md §20).
 * ``pcm16_ref`` / ``mulaw_ref``: 16-bit PCM (fp32 arithmetic, round half to even) and G.711 mu-law bytes.
 * ``gain_ref``: the per-utterance gain of peak / RMS normalisation.
 """
@@ -74,6 +76,23 @@ def resample_ref(x: np.ndarray, up: int, down: int, h: np.ndarray, half: int) ->
         return np.zeros(0, dtype=np.float64)
     P = polyphase(np.asarray(h, dtype=np.float64), half, up)
     c = half + np.arange(n_out, dtype=np.int64) * down
+    k = (c // up)[:, None] - np.arange(P.shape[1], dtype=np.int64)[None, :]
+    ok = (k >= 0) & (k < n)
+    xg = np.where(ok, x[np.clip(k, 0, n - 1)], 0.0)
+    return (P[c % up] * xg).sum(axis=1)
+
+
+def resample_range_ref(x: np.ndarray, up: int, down: int, h: np.ndarray, half: int, m_lo: int, m_hi: int) -> np.ndarray:
+    """The outputs [m_lo, min(m_hi, ceil(n up / down))) of ``resample_ref(x, ...)``, x [n], evaluated alone: the same
+    sum per output, with phase and input span from the output's own index m (mt_resample_range's specification).
+    It reads no sample of x past (half + (m_hi - 1) down) // up, so those may still be unwritten (NaN)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = x.shape[0]
+    m_lo, m_hi = max(int(m_lo), 0), min(int(m_hi), out_length(n, up, down))
+    if m_hi <= m_lo:
+        return np.zeros(0, dtype=np.float64)
+    P = polyphase(np.asarray(h, dtype=np.float64), half, up)
+    c = half + np.arange(m_lo, m_hi, dtype=np.int64) * down
     k = (c // up)[:, None] - np.arange(P.shape[1], dtype=np.int64)[None, :]
     ok = (k >= 0) & (k < n)
     xg = np.where(ok, x[np.clip(k, 0, n - 1)], 0.0)

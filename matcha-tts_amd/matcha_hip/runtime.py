@@ -947,6 +947,84 @@ def encode_audio(audio: torch.Tensor, lengths=None, normalize=None, level=None, 
     return out, gain
 
 
+def resample_range(audio: torch.Tensor, plan: ResamplePlan, lengths, lmul: int, m_lo: int, cnt: int,
+                   out: Optional[torch.Tensor] = None):
+    """The outputs [m_lo, m_lo + cnt) of ``resample``'s rows -> (out fp32 [B, cnt], out_cnt int32 [B]), bit for bit,
+    zero past a row's own output count (mt_resample_range). Of a row it reads no sample past the one the chain of its
+    last requested output starts at, so the rest of `audio` may still be unwritten (streaming delivery, DESIGN.md
+    §20). audio must be fp32 and contiguous: it is read in place."""
+    require_gpu(audio, what="resample_range")
+    if audio.dtype != torch.float32 or not audio.is_contiguous() or audio.dim() != 2:
+        raise ValueError("resample_range: audio is a contiguous fp32 [B, L] tensor")
+    B, L = audio.shape
+    m_lo, cnt = int(m_lo), int(cnt)
+    if m_lo < 0 or cnt < 1:
+        raise ValueError(f"resample_range: outputs [{m_lo}, {m_lo} + {cnt})")
+    lens = _lens32(lengths, B, audio.device)
+    if out is None:
+        out = torch.empty((B, cnt), dtype=torch.float32, device=audio.device)
+    elif out.shape != (B, cnt) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"resample_range: out {tuple(out.shape)}: expected contiguous fp32 ({B}, {cnt})")
+    out_cnt = torch.empty((B,), dtype=torch.int32, device=audio.device)
+    L_ = lib()
+    taps = plan.taps if plan.taps.device == audio.device else plan.taps.to(audio.device)
+    ws = _Workspace.get(L_.mt_resample_workspace_bytes(plan.half, plan.up, plan.down), audio.device)
+    check(L_.mt_resample_range(ptr(audio), B, L, ptr(lens), int(lmul), ptr(taps), plan.half, plan.up, plan.down, m_lo,
+                               cnt, ptr(out), ptr(out_cnt), ws.data_ptr(), ws.numel(), stream_handle(audio.device)),
+          "resample_range")
+    return out, out_cnt
+
+
+def _table(t: torch.Tensor, R: int, device, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != device or t.shape != (R,) \
+            or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous int32 [{R}] tensor on {device} expected")
+    return t
+
+
+def window_gather(src: torch.Tensor, row_src: torch.Tensor, row_start: torch.Tensor, row_len: torch.Tensor, W: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src fp32 [Bs, C, Ls] or [Bs, Ls] -> rows [R, C, W] / [R, W]: rows[r, c, w] = src[row_src[r], c, row_start[r] +
+    w] for w < row_len[r], else 0 (mt_window_gather). The tables are int32 [R] on src's device; src is read in
+    place (contiguous fp32). R <= RAGGED_MAX_BATCH."""
+    require_gpu(src, what="window_gather")
+    if src.dtype != torch.float32 or not src.is_contiguous() or src.dim() not in (2, 3):
+        raise ValueError("window_gather: src is a contiguous fp32 [B, C, L] or [B, L] tensor")
+    Bs, Ls = src.shape[0], src.shape[-1]
+    C = src.shape[1] if src.dim() == 3 else 1
+    R, W = int(row_src.shape[0]), int(W)
+    if not (1 <= R <= RAGGED_MAX_BATCH) or W < 1:
+        raise ValueError(f"window_gather: {R} rows (1..{RAGGED_MAX_BATCH}) of {W}")
+    tabs = [_table(t, R, src.device, "window_gather") for t in (row_src, row_start, row_len)]
+    shape = (R, C, W) if src.dim() == 3 else (R, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"window_gather: out {tuple(out.shape)}: expected contiguous fp32 {shape}")
+    check(lib().mt_window_gather(ptr(src), Bs, C, Ls, ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), R, W, ptr(out),
+                                 stream_handle(src.device)), "window_gather")
+    return out
+
+
+def window_scatter(rows: torch.Tensor, row_dst: torch.Tensor, crop_from: torch.Tensor, dst_start: torch.Tensor,
+                   crop_len: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """dst[row_dst[r], dst_start[r] + i] = rows[r, crop_from[r] + i] for i < crop_len[r] (mt_window_scatter): rows
+    fp32 [R, W] (or [R, 1, W]), dst fp32 [Bd, Ld], both contiguous; the tables int32 [R] on their device."""
+    require_gpu(rows, dst, what="window_scatter")
+    if rows.dim() == 3 and rows.shape[1] == 1:
+        rows = rows[:, 0]
+    for t, name in ((rows, "rows"), (dst, "dst")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"window_scatter: {name} is a contiguous fp32 2-D tensor")
+    R, W = rows.shape
+    if not (1 <= R <= RAGGED_MAX_BATCH):
+        raise ValueError(f"window_scatter: {R} rows (1..{RAGGED_MAX_BATCH})")
+    tabs = [_table(t, R, dst.device, "window_scatter") for t in (row_dst, crop_from, dst_start, crop_len)]
+    check(lib().mt_window_scatter(ptr(rows), R, W, ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), ptr(tabs[3]), ptr(dst),
+                                  dst.shape[0], dst.shape[1], stream_handle(dst.device)), "window_scatter")
+    return dst
+
+
 def maximum_path(neg_cent: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """train_standalone.py:280-325 on the GPU: neg_cent [B,Tx,Ty], attention mask [B,Tx,Ty] (x_mask x
     y_mask) -> one-hot monotonic path [B,Tx,Ty] in neg_cent's dtype. The lengths are the mask's row /
