@@ -18,6 +18,7 @@
  *                                   MOS_audiou_generator.ipynb:265-277) for a whole padded batch in one launch chain
  *   mt_resample, mt_audio_stats, <- the host steps after the vocoder, main.py:198-201 (`.clamp(-1, 1)`, soundfile's
  *   mt_audio_encode                 PCM16 write), plus rate conversion and level, which the reference leaves to callers
+ *   mt_loudness, mt_true_peak    <- no counterpart: BS.1770 loudness and true peak of the output, for delivery levels
  *   mt_window_gather,            <- streaming delivery of the steps above (windows of the mel / the audio, the outputs
  *   mt_window_scatter,              that became final): no counterpart in the reference, which vocodes whole utterances
  *   mt_resample_range
@@ -382,6 +383,30 @@ int mt_audio_stats(const float* audio, int B, int L, const int32_t* lens, float*
  * place. gain_out fp32 [B], may be NULL. */
 int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const float* peak, const double* meansq,
                     int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream);
+/* Programme loudness and true peak of every row (matcha_hip/loudness.py is the specification on the
+ * CPU). lens as in mt_audio_stats; a row's results depend on its valid samples alone, bit for bit. Neither entry point
+ * allocates on the device; every argument error is refused before any launch.
+ *
+ * mt_loudness: ITU-R BS.1770 gated loudness as an energy. The row is K-weighted from a zero state by the two biquads
+ * coef (HOST pointer to 10 doubles: b1[0..2], a1[1..2], b2[0..2], a2[1..2], a[0] = 1; transposed direct form II) in
+ * fp64, as a chunked scan along time (chunks of 32 samples, tiles of 8192, both counted from the row's start). Blocks
+ * of 4 hop samples every hop samples (32 <= hop <= 2^24; 100 ms): len_b >= 4 hop gives J = (len_b - 4 hop) / hop + 1
+ * blocks z_j = sum y^2 / (4 hop); 0 < len_b < 4 hop one block over the whole row, z_0 = sum y^2 / len_b; an empty row
+ * none. energy[b] (fp64 [B]) = the mean of the z_j with z_j > gate_abs and z_j > 0.1 * mean{z_j > gate_abs}, summed in
+ * block order; 0 when no block passes gate_abs. Loudness = -0.691 + 10 log10 energy. nblocks[b] (int32 [B]) = J.
+ * z: fp64 [B][Jcap], written whole (0 from J on), or NULL; Jcap >= the block count of a row of L samples. L <= 2^30.
+ * Workspace: mt_loudness_workspace_bytes (0 and mt_last_error for a refused shape), 16-byte aligned. */
+size_t mt_loudness_workspace_bytes(int B, int L, int hop);
+int mt_loudness(const float* audio, int B, int L, const int32_t* lens, const double* coef, int hop, double gate_abs,
+                double* z, int Jcap, int32_t* nblocks, double* energy, void* ws, size_t ws_bytes, void* stream);
+/* tpeak[b] (fp32 [B]) = the largest magnitude of the row oversampled four times, max_m |r[m]|, m < 4 len_b, r the
+ * outputs of mt_resample at up = 4, down = 1 with the same table (taps_polyphase fp32 [4][ceil((2 half + 1) / 4)],
+ * device; 1 <= half <= 1024), bit for bit: the same chain, nothing of r is written. sample_peak (fp32 [B], device,
+ * mt_audio_stats' peak; may be NULL) is folded in: tpeak[b] = max(sample_peak[b], max |r|), the true peak. L < 2^29 -
+ * 2048. Workspace: mt_true_peak_workspace_bytes, 16-byte aligned. */
+size_t mt_true_peak_workspace_bytes(int B, int L);
+int mt_true_peak(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase, int half,
+                 const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Streaming delivery (matcha_hip/stream_plan.py is the specification of the windows): cut one window

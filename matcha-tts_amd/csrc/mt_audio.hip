@@ -17,6 +17,7 @@
 //   mt_resample_range runs the same kernel on the outputs [m_lo, m_lo + cnt) of every row (mg0 = m_lo; 0 for
 //   mt_resample): phase, table column and input span come from the output's index in the utterance, so a slice has
 //   the bits of the whole, and a tile reads no sample past the one its last output's chain starts at.
+//   The tile's staging and chain live in mt_resample.h (resample_tile), shared with true_peak_kernel (mt_loudness.hip).
 // audio_stats_kernel: peak = max |x| and the fp64 sum of x^2 over tiles of ST_TILE samples counted from the
 //   utterance's start, then audio_stats_final_kernel sums the partials of one utterance in a fixed order. No atomics.
 // audio_encode_kernel: gain from the stats (fp64, rounded to fp32), v = clamp(g x, -1, 1) in fp32, then f32 / PCM16
@@ -24,22 +25,13 @@
 #include <math.h>
 
 #include "mt_common.h"
+#include "mt_resample.h"  // the tile's staging and FMA chain, utt_len
 
 namespace mt {
 
 constexpr int RS_TN = 2048;            // outputs per resample tile (runtime.RESAMPLE_TILE)
-constexpr int RS_THREADS = 256;
-constexpr int RS_U = 4;                // outputs a thread carries at once
-constexpr int RS_LDS_MAX = 64 * 1024;  // staged variant: table + span within this, else the global-read variant
 constexpr int RS_MAX_FACTOR = 1024;
 constexpr int ST_TILE = 4096;          // samples per stats partial
-constexpr int AU_MAXB = 65535;         // grid.y
-
-__device__ __forceinline__ int utt_len(const int* lens, int b, int lmul, int L) {
-  if (!lens) return L;
-  const long long n = (long long)lens[b] * lmul;
-  return (int)(n < 0 ? 0 : (n > L ? L : n));
-}
 
 __global__ void resample_table_kernel(const float* __restrict__ taps, int up, int Q, int s, float* __restrict__ tab,
                                       int tabN) {
@@ -78,62 +70,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
     return;
   }
   const int nt = min(RS_TN, n_out - m0);   // ... and inside the utterance
-  // output m0 + j reads x[k0 + (rem0 + j down) / up - q]; kS is the first sample any output of the tile reads
-  const long long c0 = half + (long long)m0 * down;
-  const long long k0 = c0 / up;
-  const int rem0 = (int)(c0 - k0 * up);
-  const long long kS = k0 - (Q - 1);
-  const float* x = audio + (size_t)b * L;
-  float* xl = lds + tabN;  // STAGED: lds = table [Q][up] (tabN floats), then the tile's input span from kS on
-  if (STAGED) {
-    for (int i = tid * 4; i < tabN; i += RS_THREADS * 4) *(f32x4*)(lds + i) = *(const f32x4*)(tab + i);
-    const int span = (rem0 + (nt - 1) * down) / up + Q;
-    for (int i = tid; i < span; i += RS_THREADS) {
-      const long long k = kS + i;
-      xl[i] = (k >= 0 && k < len) ? x[k] : 0.f;
-    }
-    __syncthreads();
-  }
-  const int rbase = (int)((r0 + (long long)m0) % up);
-  if (STAGED) {
-    // RS_U outputs per thread at a time: independent chains keep RS_U pairs of LDS reads in flight per tap; each
-    // chain is still q = 0 .. Q - 1 on its own accumulator. An output past nt runs on output 0's operands, unstored.
-    for (int j0 = tid; j0 < nrow; j0 += RS_THREADS * RS_U) {
-      float acc[RS_U];
-      int ti[RS_U], xi[RS_U];
-#pragma unroll
-      for (int u = 0; u < RS_U; ++u) {
-        const int j = j0 + u * RS_THREADS;
-        const int jj = j < nt ? j : 0;
-        xi[u] = (rem0 + jj * down) / up + (Q - 1);  // x[k0 + (rem0 + j down) / up] relative to kS
-        ti[u] = (rbase + jj) % up;
-        acc[u] = 0.f;
-      }
-      for (int q = 0; q < Q; ++q) {
-#pragma unroll
-        for (int u = 0; u < RS_U; ++u) acc[u] = __builtin_fmaf(lds[q * up + ti[u]], xl[xi[u] - q], acc[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < RS_U; ++u) {
-        const int j = j0 + u * RS_THREADS;
-        if (j < nrow) y[j] = j < nt ? acc[u] : 0.f;
-      }
-    }
-  } else {
-    for (int j = tid; j < nrow; j += RS_THREADS) {
-      float acc = 0.f;
-      if (j < nt) {
-        const int i0 = (rem0 + j * down) / up + (Q - 1);
-        const int r = (rbase + j) % up;
-        for (int q = 0; q < Q; ++q) {
-          const long long k = kS + i0 - q;
-          const float xv = (k >= 0 && k < len) ? x[k] : 0.f;
-          acc = __builtin_fmaf(tab[(size_t)q * up + r], xv, acc);
-        }
-      }
-      y[j] = acc;
-    }
-  }
+  resample_tile<STAGED>(audio + (size_t)b * L, len, tab, tabN, half, up, down, Q, r0, m0, nt, nrow, lds,
+                        [y](int j, float v) { y[j] = v; });
 }
 
 __global__ __launch_bounds__(256) void audio_stats_kernel(const float* __restrict__ audio, int L,
@@ -278,6 +216,8 @@ __global__ __launch_bounds__(256) void audio_encode_kernel(const float* __restri
 
 static int taps_per_phase(int half, int up) { return (2 * half + 1 + up - 1) / up; }
 static size_t table_floats(int half, int up) { return ((size_t)up * taps_per_phase(half, up) + 3) & ~(size_t)3; }
+int resample_taps_per_phase(int half, int up) { return taps_per_phase(half, up); }
+size_t resample_table_floats(int half, int up) { return table_floats(half, up); }
 static int igcd(int a, int b) {
   while (b) {
     const int t = a % b;
@@ -300,6 +240,18 @@ size_t resample_workspace_bytes(int half, int up, int down) {
   return table_floats(half, up) * sizeof(float);
 }
 
+int resample_table_launch(const float* taps, int half, int up, int down, float* tab, int* r0_out, hipStream_t st) {
+  const size_t tabN = table_floats(half, up);
+  const int Q = taps_per_phase(half, up), s = down % up;
+  int r0 = 0;  // the column of output 0: its phase is half % up
+  while ((r0 * s) % up != half % up) ++r0;
+  hipLaunchKernelGGL(resample_table_kernel, dim3((unsigned)((tabN + 255) / 256)), dim3(256), 0, st, taps, up, Q, s,
+                     tab, (int)tabN);
+  MT_CHECK_HIP(hipGetLastError());
+  *r0_out = r0;
+  return 0;
+}
+
 // the table re-order, then resample_kernel on the outputs [mg0, mg0 + Lout) of every row (the callers check the rest)
 static int resample_launch(const float* audio, int B, int L, const int* lens, int lmul, const float* taps, int half,
                            int up, int down, int mg0, float* out, int Lout, int* out_lens, void* ws, size_t ws_bytes,
@@ -307,13 +259,11 @@ static int resample_launch(const float* audio, int B, int L, const int* lens, in
   const size_t tabN = table_floats(half, up);
   MT_REQUIRE(ws && ws_bytes >= tabN * sizeof(float) && ((uintptr_t)ws & 15) == 0,
              "resample: workspace too small or not 16-byte aligned");
-  const int Q = taps_per_phase(half, up), s = down % up;
-  int r0 = 0;  // the column of output 0: its phase is half % up
-  while ((r0 * s) % up != half % up) ++r0;
+  const int Q = taps_per_phase(half, up);
+  int r0 = 0;
   float* tab = (float*)ws;
-  hipLaunchKernelGGL(resample_table_kernel, dim3((unsigned)((tabN + 255) / 256)), dim3(256), 0, st, taps, up, Q, s,
-                     tab, (int)tabN);
-  MT_CHECK_HIP(hipGetLastError());
+  const int rc = resample_table_launch(taps, half, up, down, tab, &r0, st);
+  if (rc != 0) return rc;
   const size_t span_max = ((size_t)(up - 1) + (size_t)(RS_TN - 1) * down) / up + Q;
   const size_t lds = (tabN + span_max) * sizeof(float);
   const dim3 grid((Lout + RS_TN - 1) / RS_TN, B);

@@ -34,6 +34,13 @@ int audio_stats(const float* audio, int B, int L, const int* lens, float* peak, 
                 size_t ws_bytes, hipStream_t st);
 int audio_encode(const float* audio, int B, int L, const int* lens, const float* peak, const double* meansq,
                  int normalize, double level, int limit, int encoding, void* out, float* gain_out, hipStream_t st);
+// mt_loudness.hip
+size_t loudness_workspace_bytes(int B, int L, int hop);
+int loudness(const float* audio, int B, int L, const int* lens, const double* coef, int hop, double gate_abs,
+             double* z, int Jcap, int* nblocks, double* energy, void* ws, size_t ws_bytes, hipStream_t st);
+size_t true_peak_workspace_bytes(int B, int L);
+int true_peak(const float* audio, int B, int L, const int* lens, const float* taps, int half,
+              const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, hipStream_t st);
 // mt_stream.hip
 int window_gather(const float* src, int Bs, int C, int Ls, const int* row_src, const int* row_start,
                   const int* row_len, int R, int W, float* rows, hipStream_t st);
@@ -452,6 +459,20 @@ int mt_audio_encode(const float* audio, int B, int L, const int32_t* lens, const
                     int normalize, double level, int limit, int encoding, void* out, float* gain_out, void* stream) {
   return mt::audio_encode(audio, B, L, lens, peak, meansq, normalize, level, limit, encoding, out, gain_out,
                           (hipStream_t)stream);
+}
+
+// ---- loudness and true peak ----
+size_t mt_loudness_workspace_bytes(int B, int L, int hop) { return mt::loudness_workspace_bytes(B, L, hop); }
+int mt_loudness(const float* audio, int B, int L, const int32_t* lens, const double* coef, int hop, double gate_abs,
+                double* z, int Jcap, int32_t* nblocks, double* energy, void* ws, size_t ws_bytes, void* stream) {
+  return mt::loudness(audio, B, L, lens, coef, hop, gate_abs, z, Jcap, nblocks, energy, ws, ws_bytes,
+                      (hipStream_t)stream);
+}
+size_t mt_true_peak_workspace_bytes(int B, int L) { return mt::true_peak_workspace_bytes(B, L); }
+int mt_true_peak(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase, int half,
+                 const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, void* stream) {
+  return mt::true_peak(audio, B, L, lens, taps_polyphase, half, sample_peak, tpeak, ws, ws_bytes,
+                       (hipStream_t)stream);
 }
 
 // ---- streaming delivery: window gather / scatter ----

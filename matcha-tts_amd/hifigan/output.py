@@ -10,14 +10,22 @@ to soundfile; rate, level and encoding are left to the caller there). No counter
 Three HIP launches on the whole batch (mt_resample, mt_audio_stats, mt_audio_encode); row b of the result is, bit for
 bit, what the same call returns for that utterance alone (matcha_hip/audio_out.py is the
 specification on the CPU).
+
+    out = AudioOutput(16000, loudness=-16.0, true_peak=-1.0, encoding="pcm16")(wav, lengths)
+
+levels every utterance to -16 LUFS (ITU-R BS.1770 gated loudness) with its true peak held at or under -1 dBTP
+(mt_loudness and mt_true_peak in place of mt_audio_stats; DESIGN.md §21, matcha_hip/loudness.py), and
+`AudioOutput(16000).measure(wav, lengths)` reports both figures of what the stage would deliver at gain 1.
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple, Optional
 
 import torch
 
 from matcha_hip import audio_out
+from matcha_hip import loudness as ld
 from matcha_hip import runtime as rt
 
 
@@ -28,17 +36,26 @@ class AudioOut(NamedTuple):
     gain: torch.Tensor           # fp32 [B], the gain each row was multiplied by
 
 
+class Loudness(NamedTuple):
+    lufs: torch.Tensor           # fp64 [B], gated loudness; -inf for a silent, empty or fully gated row
+    true_peak_db: torch.Tensor   # fp64 [B], dBTP; -inf for a silent or empty row
+    lengths: torch.Tensor        # int32 [B], the measured samples of each row at sample_rate
+    sample_rate: int
+
+
 class AudioOutput:
     """sample_rate / source_rate: any pair whose reduced factor up/down has both parts <= 1024 (from 22,050 Hz: 8000,
     11025, 16000, 24000, 32000, 44100, 48000, ...), Kaiser-windowed sinc with `zeros` zero crossings per side at the
     lower rate and Kaiser `beta` (scipy.signal.resample_poly's default design). normalize: None, "peak" (the row's
     peak becomes `level`, default 0.95) or "rms" (its RMS becomes `level`, default -20 dBFS; with `limit` the gain
     stops where the peak would pass full scale). encoding: "f32", "pcm16" or "mulaw" (G.711). Level and encoding are
-    measured on, and applied to, the resampled signal."""
+    measured on, and applied to, the resampled signal. loudness: a target in LUFS (-70 < target <= 0, ITU-R BS.1770
+    gated loudness; needs normalize=None and sample_rate >= 8000): the row's loudness becomes the target, and with
+    `limit` the gain stops where the row's true peak (4x oversampled) would pass `true_peak` dBTP (<= 0)."""
 
     def __init__(self, sample_rate: int = 22050, source_rate: int = 22050, normalize: Optional[str] = None,
                  level: Optional[float] = None, limit: bool = True, encoding: str = "f32", zeros: int = 10,
-                 beta: float = 5.0, hop: int = 256):
+                 beta: float = 5.0, hop: int = 256, loudness: Optional[float] = None, true_peak: float = -1.0):
         if normalize not in rt.NORMALIZE_CODES:
             raise ValueError(f"normalize must be one of {list(rt.NORMALIZE_CODES)}, got {normalize!r}")
         if encoding not in rt.ENCODING_CODES:
@@ -50,24 +67,66 @@ class AudioOutput:
         self.sample_rate, self.source_rate = int(sample_rate), int(source_rate)
         self.normalize, self.level, self.limit, self.encoding = normalize, level, bool(limit), encoding
         self.zeros, self.beta, self.hop = int(zeros), float(beta), int(hop)
+        true_peak = float(true_peak)
+        if not (math.isfinite(true_peak) and true_peak <= 0.0):
+            raise ValueError(f"true_peak must be a finite ceiling in dBTP at or under 0, got {true_peak}")
+        if loudness is not None:
+            loudness = float(loudness)
+            if normalize is not None:
+                raise ValueError(f"loudness={loudness} and normalize={normalize!r} both set the level: use one")
+            if not (math.isfinite(loudness) and -70.0 < loudness <= 0.0):
+                raise ValueError(f"loudness must be a finite target in LUFS with -70 < target <= 0, got {loudness}")
+            if self.sample_rate < ld.MIN_RATE:
+                raise ValueError(f"loudness: sample_rate {self.sample_rate} is below {ld.MIN_RATE} Hz, the lowest "
+                                 "rate the K-weighting is designed for")
+        self.loudness, self.true_peak = loudness, true_peak
+
+    def _resampled(self, audio: torch.Tensor, lengths, what: str):
+        """-> (audio [B, L_out] at sample_rate, lens int32 [B] in samples)"""
+        rt.require_gpu(audio, what=what)
+        if audio.dim() == 3 and audio.shape[1] == 1:
+            audio = audio[:, 0]
+        if audio.dim() != 2:
+            raise ValueError(f"{what}: audio {tuple(audio.shape)}, expected [B, L] or [B, 1, L]")
+        B, L = audio.shape
+        if self.sample_rate != self.source_rate:
+            plan = rt.resample_plan(self.source_rate, self.sample_rate, self.zeros, self.beta, audio.device)
+            return rt.resample(audio, plan, lengths, lmul=self.hop)
+        if lengths is None:
+            return audio, torch.full((B,), L, dtype=torch.int32, device=audio.device)
+        lens = (torch.as_tensor(lengths).to(device=audio.device, dtype=torch.int64) * self.hop).clamp_(0, L)
+        return audio, lens.to(torch.int32)
+
+    def _measure(self, audio: torch.Tensor, lens: torch.Tensor):
+        """-> (E fp64 [B], TP fp32 [B]) of rows at sample_rate"""
+        if self.sample_rate < ld.MIN_RATE:
+            raise ValueError(f"loudness: sample_rate {self.sample_rate} is below {ld.MIN_RATE} Hz")
+        energy, _ = rt.loudness(audio, lens, self.sample_rate)
+        plan4 = rt.resample_plan(self.sample_rate, 4 * self.sample_rate, self.zeros, self.beta, audio.device)
+        return energy, rt.true_peak(audio, lens, plan4)
+
+    @torch.inference_mode()
+    def measure(self, audio: torch.Tensor, lengths=None) -> Loudness:
+        """Loudness (LUFS) and true peak (dBTP) of each row as the stage delivers it at gain 1: measured after the
+        rate conversion, before any level. audio and lengths as in __call__. The two log10 are for reporting; the
+        gain of `loudness=` is computed from the energies themselves."""
+        audio, lens = self._resampled(audio, lengths, "AudioOutput.measure")
+        energy, tp = self._measure(audio, lens)
+        return Loudness(10.0 * torch.log10(energy) - 0.691, 20.0 * torch.log10(tp.double()), lens, self.sample_rate)
 
     @torch.inference_mode()
     def __call__(self, audio: torch.Tensor, lengths=None) -> AudioOut:
         """audio [B, L] or [B, 1, L] at source_rate; lengths int [B] in mel frames (x hop = 256 samples), as
         Generator.forward and Denoiser.forward take it; None: every row is L samples long."""
-        rt.require_gpu(audio, what="AudioOutput")
-        if audio.dim() == 3 and audio.shape[1] == 1:
-            audio = audio[:, 0]
-        if audio.dim() != 2:
-            raise ValueError(f"AudioOutput: audio {tuple(audio.shape)}, expected [B, L] or [B, 1, L]")
-        B, L = audio.shape
-        if self.sample_rate != self.source_rate:
-            plan = rt.resample_plan(self.source_rate, self.sample_rate, self.zeros, self.beta, audio.device)
-            audio, lens = rt.resample(audio, plan, lengths, lmul=self.hop)
-        elif lengths is None:
-            lens = torch.full((B,), L, dtype=torch.int32, device=audio.device)
-        else:
-            lens = (torch.as_tensor(lengths).to(device=audio.device, dtype=torch.int64) * self.hop).clamp_(0, L)
-            lens = lens.to(torch.int32)
-        out, gain = rt.encode_audio(audio, lens, self.normalize, self.level, self.limit, self.encoding)
+        audio, lens = self._resampled(audio, lengths, "AudioOutput")
+        if self.loudness is None:
+            out, gain = rt.encode_audio(audio, lens, self.normalize, self.level, self.limit, self.encoding)
+            return AudioOut(out, lens, self.sample_rate, gain)
+        # loudness.loudness_gain_ref through gain_ref's "rms" branch: the mean square is the gated energy, the level
+        # the target's RMS, and the peak is the true peak over the ceiling, so that 1 / peak caps the gain at c / TP
+        energy, tp = self._measure(audio, lens)
+        peak_eff = (tp.double() / 10.0 ** (self.true_peak / 20.0)).float()
+        peak_eff = torch.where(energy > 0, peak_eff, torch.zeros_like(peak_eff))  # nothing to level: gain 1
+        out, gain = rt.encode_audio(audio, lens, "rms", ld.target_level(self.loudness), self.limit, self.encoding,
+                                    stats=(peak_eff, energy))
         return AudioOut(out, lens, self.sample_rate, gain)

@@ -29,7 +29,8 @@ fp32 tensor: a caller may fill it in as the stream advances (``WaveStreamer.sche
 The loop does not synchronise with the host: `lengths` is fetched once at the start, the tables of all steps are
 uploaded once, and each step enqueues a fixed chain for the whole batch: gather -> mt_vocoder_forward_ragged ->
 scatter -> gather -> mt_denoise_ragged -> scatter -> mt_resample_range -> mt_audio_encode. Not streamed: the CFM solve
-(global over the utterance) and level normalisation (`normalize="peak"` / `"rms"` need the whole utterance).
+(global over the utterance) and level normalisation (`normalize="peak"` / `"rms"` and `loudness=` need the whole
+utterance).
 """
 from __future__ import annotations
 
@@ -60,6 +61,10 @@ class WaveStreamer:
             raise ValueError(f"WaveStreamer: normalize={output.normalize!r} takes its gain from the peak / RMS of the "
                              "whole utterance, which a stream has not seen when it delivers the first chunk; "
                              "normalise the level after the stream, or use normalize=None")
+        if output is not None and getattr(output, "loudness", None) is not None:
+            raise ValueError(f"WaveStreamer: loudness={output.loudness!r} takes its gain from the gated loudness and "
+                             "the true peak of the whole utterance, which a stream has not seen when it delivers "
+                             "the first chunk; level the loudness after the stream, or use loudness=None")
         eng = generator.engine()
         self.per_row = generator.precision in ("fp32", "float32", "f32")
         if not self.per_row and not eng.ragged_supported():

@@ -9,7 +9,7 @@ from __future__ import annotations
 import math
 import numbers
 import time
-from ctypes import byref, c_char_p, c_int, c_int32, c_int64, c_void_p, create_string_buffer
+from ctypes import byref, c_char_p, c_double, c_int, c_int32, c_int64, c_void_p, create_string_buffer
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -945,6 +945,58 @@ def encode_audio(audio: torch.Tensor, lengths=None, normalize=None, level=None, 
                                 level, int(bool(limit)), code, ptr(out), ptr(gain), stream_handle(audio.device)),
           "audio_encode")
     return out, gain
+
+
+# ---- loudness and true peak (loudness.py is the specification) ---------------------------------
+
+# samples per chunk and per tile of the K-weighting scan (mt_loudness.hip KW_CH, KW_TILE): tests put row ends around
+# their multiples
+LOUDNESS_CHUNK = 32
+LOUDNESS_TILE = 8192
+
+
+def loudness(audio: torch.Tensor, lengths, sample_rate: int, return_blocks: bool = False):
+    """audio [B, L] at sample_rate, lengths in samples (int [B], or None = L) -> (energy fp64 [B], nblocks int32 [B])
+    and, with return_blocks, z fp64 [B, J(L)]: the gated mean square of each row's K-weighted signal
+    (loudness.gate_ref of its block energies z; LUFS = -0.691 + 10 log10 energy), its block count, its blocks, zero
+    from nblocks[b] on (mt_loudness)."""
+    from . import loudness as ld
+    coef = ld.coefficients(sample_rate)  # ValueError below 8 kHz
+    require_gpu(audio, what="loudness")
+    hop = ld.hop_of(sample_rate)
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    energy = torch.empty((B,), dtype=torch.float64, device=audio.device)
+    nblocks = torch.empty((B,), dtype=torch.int32, device=audio.device)
+    Jcap = max(ld.block_count(L, sample_rate), 1)
+    z = torch.empty((B, Jcap), dtype=torch.float64, device=audio.device) if return_blocks else None
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_loudness_workspace_bytes(B, L, hop), audio.device)
+    check(L_.mt_loudness(ptr(audio), B, L, ptr(lens), (c_double * 10)(*coef.tolist()), hop, ld.ABS_GATE, ptr(z),
+                         Jcap, ptr(nblocks), ptr(energy), ws.data_ptr(), ws.numel(), stream_handle(audio.device)),
+          "loudness")
+    return (energy, nblocks, z) if return_blocks else (energy, nblocks)
+
+
+def true_peak(audio: torch.Tensor, lengths, plan4: ResamplePlan) -> torch.Tensor:
+    """audio [B, L], lengths in samples (int [B], or None = L), plan4 = resample_plan(fs, 4 fs) -> fp32 [B]: the
+    larger of each row's sample peak (mt_audio_stats) and of the peak of its 4x oversampled signal, which has the bits
+    of resample(audio, plan4) and is never written (mt_true_peak)."""
+    require_gpu(audio, what="true_peak")
+    if (plan4.up, plan4.down) != (4, 1):
+        raise ValueError(f"true_peak: the plan is {plan4.up}/{plan4.down}; the true peak is measured at 4/1")
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    peak, _ = audio_stats(audio, lens)
+    tpeak = torch.empty((B,), dtype=torch.float32, device=audio.device)
+    L_ = lib()
+    taps = plan4.taps if plan4.taps.device == audio.device else plan4.taps.to(audio.device)
+    ws = _Workspace.get(L_.mt_true_peak_workspace_bytes(B, L), audio.device)
+    check(L_.mt_true_peak(ptr(audio), B, L, ptr(lens), ptr(taps), plan4.half, ptr(peak), ptr(tpeak), ws.data_ptr(),
+                          ws.numel(), stream_handle(audio.device)), "true_peak")
+    return tpeak
 
 
 def resample_range(audio: torch.Tensor, plan: ResamplePlan, lengths, lmul: int, m_lo: int, cnt: int,

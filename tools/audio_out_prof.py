@@ -3,7 +3,8 @@
     rocprofv3 --kernel-trace --stats -d OUT -o run --output-format csv -- python tools/audio_out_prof.py --rate 16000
 
 B utterances at synthetic.ljspeech_lengths (mel frames, x 256 samples) in one padded [B, L] buffer of noise; each
-iteration runs the ragged denoiser (the stage this one follows, for comparison) and AudioOutput(rate, "peak", "pcm16").
+iteration runs the ragged denoiser (the stage this one follows, for comparison) and AudioOutput(rate, "peak", "pcm16");
+with --loudness LUFS also AudioOutput(rate, loudness=LUFS) (the K-weighting scan and the true peak).
 Prints one JSON line: the shapes, and the bytes each launch has to move with their time at the HBM rate DESIGN.md §4
 uses. Kernel times come from the trace, not from this script.
 """
@@ -28,6 +29,8 @@ def main():
     p.add_argument("--iters", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--encoding", default="pcm16")
+    p.add_argument("--loudness", type=float, default=None,
+                   help="also run AudioOutput(rate, loudness=LUFS) on the same batch each iteration (DESIGN.md §21)")
     a = p.parse_args()
     from hifigan.output import AudioOutput
     from matcha_hip import audio_out, synthetic
@@ -40,9 +43,12 @@ def main():
     ld = torch.from_numpy(lens.astype(np.int32)).to(dev)
     bias = torch.rand(513, generator=g).to(dev)
     stage = AudioOutput(a.rate, normalize="peak", encoding=a.encoding)
+    leveled = None if a.loudness is None else AudioOutput(a.rate, loudness=a.loudness, encoding=a.encoding)
     for _ in range(a.warmup + a.iters):
         d = rt.denoise(audio, bias, 0.00025, lengths=ld)
         out = stage(d, ld)
+        if leveled is not None:
+            leveled(d, ld)
     torch.cuda.synchronize()
     up, down = audio_out.rates(22050, a.rate)
     n_in = int(256 * lens.sum())
