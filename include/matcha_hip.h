@@ -22,6 +22,8 @@
  *   mt_window_gather,            <- streaming delivery of the steps above (windows of the mel / the audio, the outputs
  *   mt_window_scatter,              that became final): no counterpart in the reference, which vocodes whole utterances
  *   mt_resample_range
+ *   mt_audio_edges, mt_join_plan, <- long-form synthesis: a batch of sentences joined into documents (trim, pauses,
+ *   mt_join                         crossfades); no counterpart in the reference, which writes one file per sentence
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
  *   mt_durations_tokens, mt_align   duration control and a forced aligner for inference: no counterpart in the
  *                                   reference (its log-prior train_standalone.py:639-644 in direct form, textbook MAS)
@@ -423,6 +425,49 @@ int mt_window_gather(const float* src, int Bs, int C, int Ls, const int32_t* row
  * [Bd][Ld]; the rest of dst keeps its contents. Two rows r must not write the same samples of dst. */
 int mt_window_scatter(const float* rows, int R, int W, const int32_t* row_dst, const int32_t* crop_from,
                       const int32_t* dst_start, const int32_t* crop_len, float* dst, int Bd, int Ld, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Long-form synthesis (matcha_hip/join.py is the specification on the CPU): a batch of sentences
+ * (segments, the rows of seg fp32 [S][L]) becomes D documents: trim edges per segment, the place of every segment in
+ * its document, the documents written with fades and overlaps. 1 <= S, D <= 65535; L, Ld, Lcap <= 2^30. doc_first:
+ * int32 [D + 1], CSR: document d owns the segments doc_first[d] .. doc_first[d + 1] - 1 in that order (none is
+ * allowed). All tables are int32 in device memory, so mt_audio_edges -> mt_join_plan -> mt_join needs no host round
+ * trip; the host cannot check them, and an entry that points outside its buffer (a segment range outside [0, S], an
+ * edge outside [0, L], a doc_len past Ld) is clamped inside the kernels: wrong audio, never an access out of range.
+ * No entry point allocates on the device, none uses atomics, every argument error is refused before any launch, and
+ * a document's results depend on its own segments alone, bit for bit.
+ * ------------------------------------------------------------------------------------- */
+/* Trim edges of every row: sample k < n_s (n_s = lens[s] clamped to [0, L]; lens int32 [S], NULL: L) is loud when
+ * |audio[s][k]| >= thr (fp32 compare; a NaN is not loud; thr finite, >= 0). first / last = the smallest / largest
+ * loud k: start[s] = max(first - pad, 0), end[s] = min(last + 1 + pad, n_s) (pad >= 0, in samples); (0, 0) for a row
+ * without a loud sample. One pass over tiles of 4096 samples counted from the row's start; tiles at or past n_s are
+ * skipped and nothing at or past n_s is read. Integer min / max through the workspace (two ints per tile), then one
+ * workgroup per row. Workspace: mt_audio_edges_workspace_bytes (0 and mt_last_error for a refused shape), 16-byte
+ * aligned. start, end: int32 [S]. */
+size_t mt_audio_edges_workspace_bytes(int S, int L);
+int mt_audio_edges(const float* audio, int S, int L, const int32_t* lens, float thr, int pad, int32_t* start,
+                   int32_t* end, void* ws, size_t ws_bytes, void* stream);
+/* Placement. Per segment a_s = clamp(start[s], 0, L), e_s = clamp(end[s], a_s, L), len_s = e_s - a_s. gap[s] (int32
+ * [S]) is the silence in samples between s and the next segment of its document, negative an overlap; it is ignored on
+ * a document's last segment. Effective gap g_s = max(gap[s], -min(len_s / 2, len_{s+1} / 2)) (integer halves), so no
+ * sample is covered by more than two segments. dst[first] = head, dst[s + 1] = dst[s] + len_s + g_s; doc_len[d] =
+ * dst[last] + len_last + tail, head + tail for a document without segments (head, tail >= 0). 64-bit arithmetic;
+ * *bad (int32, device) = 1 when a doc_len exceeds Lcap (1 .. 2^30), else 0, and every output is then min(., Lcap) of
+ * its 64-bit value: nothing wraps. dst int32 [S] (a segment no document owns is not written), doc_len int32 [D]. One
+ * workgroup per document: a segmented scan in chunks of 256 segments. */
+int mt_join_plan(const int32_t* doc_first, int D, const int32_t* start, const int32_t* end, const int32_t* gap, int S,
+                 int L, int head, int tail, int Lcap, int32_t* dst, int32_t* doc_len, int32_t* bad, void* stream);
+/* out[d][i] (fp32 [D][Ld], written whole) = 0.0f plus, in segment order, fl32(w_s(j) seg[s][a_s + j]) for every
+ * segment s of document d with 0 <= j = i - dst[s] < len_s: one fp32 product and one fp32 add per covering segment,
+ * rounded separately (never a fused multiply-add); zero where nothing covers i and from min(doc_len[d], Ld) on. With
+ * F_s = min(fade, len_s / 2): w_s(j) = ramp[((2 j + 1) fade) / (2 F_s)] for j < F_s, the same of j' = len_s - 1 - j
+ * for j >= len_s - F_s, 1 between (with F_s == fade the index is j itself). ramp: fp32 [fade], device, the rising
+ * half of a raised cosine 0.5 - 0.5 cos(pi (j + 0.5) / fade) built by the host; 0 <= fade <= 16384, NULL allowed at
+ * fade == 0. Only the samples [a_s, e_s) of a segment are read. One workgroup per tile of 1024 document samples: it
+ * finds its first segment by binary search in the document's range of dst (non-decreasing in a plan of mt_join_plan)
+ * and walks forward. */
+int mt_join(const float* seg, int S, int L, const int32_t* start, const int32_t* end, const int32_t* doc_first, int D,
+            const int32_t* dst, const int32_t* doc_len, const float* ramp, int fade, float* out, int Ld, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Log-mel featurizer (§8f rank 4), replacing train_standalone.py:164-201 `mel_spectrogram(y, 1024, 80,

@@ -46,6 +46,14 @@ int window_gather(const float* src, int Bs, int C, int Ls, const int* row_src, c
                   const int* row_len, int R, int W, float* rows, hipStream_t st);
 int window_scatter(const float* rows, int R, int W, const int* row_dst, const int* crop_from, const int* dst_start,
                    const int* crop_len, float* dst, int Bd, int Ld, hipStream_t st);
+// mt_join.hip
+size_t audio_edges_workspace_bytes(int S, int L);
+int audio_edges(const float* audio, int S, int L, const int* lens, float thr, int pad, int* start, int* end, void* ws,
+                size_t ws_bytes, hipStream_t st);
+int join_plan(const int* doc_first, int D, const int* start, const int* end, const int* gap, int S, int L, int head,
+              int tail, int Lcap, int* dst, int* doc_len, int* bad, hipStream_t st);
+int join(const float* seg, int S, int L, const int* start, const int* end, const int* doc_first, int D, const int* dst,
+         const int* doc_len, const float* ramp, int fade, float* out, int Ld, hipStream_t st);
 }  // namespace mt
 
 struct mt_encoder {
@@ -483,6 +491,21 @@ int mt_window_gather(const float* src, int Bs, int C, int Ls, const int32_t* row
 int mt_window_scatter(const float* rows, int R, int W, const int32_t* row_dst, const int32_t* crop_from,
                       const int32_t* dst_start, const int32_t* crop_len, float* dst, int Bd, int Ld, void* stream) {
   return mt::window_scatter(rows, R, W, row_dst, crop_from, dst_start, crop_len, dst, Bd, Ld, (hipStream_t)stream);
+}
+
+// ---- long-form synthesis: trim edges, placement, join ----
+size_t mt_audio_edges_workspace_bytes(int S, int L) { return mt::audio_edges_workspace_bytes(S, L); }
+int mt_audio_edges(const float* audio, int S, int L, const int32_t* lens, float thr, int pad, int32_t* start,
+                   int32_t* end, void* ws, size_t ws_bytes, void* stream) {
+  return mt::audio_edges(audio, S, L, lens, thr, pad, start, end, ws, ws_bytes, (hipStream_t)stream);
+}
+int mt_join_plan(const int32_t* doc_first, int D, const int32_t* start, const int32_t* end, const int32_t* gap, int S,
+                 int L, int head, int tail, int Lcap, int32_t* dst, int32_t* doc_len, int32_t* bad, void* stream) {
+  return mt::join_plan(doc_first, D, start, end, gap, S, L, head, tail, Lcap, dst, doc_len, bad, (hipStream_t)stream);
+}
+int mt_join(const float* seg, int S, int L, const int32_t* start, const int32_t* end, const int32_t* doc_first, int D,
+            const int32_t* dst, const int32_t* doc_len, const float* ramp, int fade, float* out, int Ld, void* stream) {
+  return mt::join(seg, S, L, start, end, doc_first, D, dst, doc_len, ramp, fade, out, Ld, (hipStream_t)stream);
 }
 
 size_t mt_maximum_path_workspace_bytes(int B, int Tx, int Ty) { return mt::mas_workspace_bytes(B, Tx, Ty); }

@@ -119,6 +119,16 @@ class AudioOutput:
         """audio [B, L] or [B, 1, L] at source_rate; lengths int [B] in mel frames (x hop = 256 samples), as
         Generator.forward and Denoiser.forward take it; None: every row is L samples long."""
         audio, lens = self._resampled(audio, lengths, "AudioOutput")
+        return self.finish(audio, lens)
+
+    @torch.inference_mode()
+    def finish(self, audio: torch.Tensor, lens_samples: torch.Tensor) -> AudioOut:
+        """The level-and-encode half of __call__: audio fp32 [B, L] already at sample_rate, lens_samples int32 [B] in
+        samples. What __call__ runs after its rate conversion, and what LongForm runs on joined documents."""
+        rt.require_gpu(audio, what="AudioOutput.finish")
+        if audio.dim() != 2:
+            raise ValueError(f"AudioOutput.finish: audio {tuple(audio.shape)}, expected [B, L]")
+        lens = lens_samples
         if self.loudness is None:
             out, gain = rt.encode_audio(audio, lens, self.normalize, self.level, self.limit, self.encoding)
             return AudioOut(out, lens, self.sample_rate, gain)

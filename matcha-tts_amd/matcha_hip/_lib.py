@@ -105,6 +105,10 @@ SIGNATURES = {
     "mt_loudness": (c_int, [P, c_int, c_int, P, POINTER(c_double), c_int, c_double, P, c_int, P, P, P, c_size_t, P]),
     "mt_true_peak_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mt_true_peak": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P, c_size_t, P]),
+    "mt_audio_edges_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mt_audio_edges": (c_int, [P, c_int, c_int, P, c_float, c_int, P, P, P, c_size_t, P]),
+    "mt_join_plan": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "mt_join": (c_int, [P, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P, c_int, P]),
     "mt_maximum_path_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mt_decoder_step_times_workspace_bytes": (c_size_t, [P, c_int, c_int]),
     "mt_decoder_step_times": (c_int, [P, P, P, P, P, P, P, c_int, c_int, P, P, c_size_t, P]),

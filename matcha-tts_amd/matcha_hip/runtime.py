@@ -1077,6 +1077,107 @@ def window_scatter(rows: torch.Tensor, row_dst: torch.Tensor, crop_from: torch.T
     return dst
 
 
+# ---- long-form synthesis: trim edges, placement, join (join.py is the specification) ------------
+
+# samples per workgroup of edges_tile_kernel (ED_TILE), segments per scan step of join_plan_kernel (JP_CHUNK) and
+# document samples per workgroup of join_kernel (JN_TILE), all in mt_join.hip: tests put lengths around their multiples
+EDGES_TILE = 4096
+JOIN_PLAN_CHUNK = 256
+JOIN_TILE = 1024
+JOIN_MAX_ROWS = 65535
+
+_RAMPS: Dict[tuple, torch.Tensor] = {}
+
+
+def _ramp_table(fade: int, device) -> Optional[torch.Tensor]:
+    """join.ramp(fade) on the device, cached per (fade, device): built on the host, as the resampler's taps are"""
+    from . import join as jn
+    table = jn.ramp(fade)  # ValueError for a fade the kernel does not take
+    if fade == 0:
+        return None
+    key = (int(fade), device.index)
+    t = _RAMPS.get(key)
+    if t is None:
+        t = _RAMPS[key] = torch.from_numpy(table).to(device)
+    return t
+
+
+def audio_edges(audio: torch.Tensor, lengths, thr: float, pad: int):
+    """audio [S, L], lengths in samples (int [S], or None = L) -> (start, end) int32 [S]: join.edges_ref of every
+    row (mt_audio_edges). audio is read in place when it is contiguous fp32."""
+    require_gpu(audio, what="audio_edges")
+    thr, pad = float(thr), int(pad)
+    if not (math.isfinite(thr) and thr >= 0.0) or pad < 0:
+        raise ValueError(f"audio_edges: thr {thr} (finite, >= 0), pad {pad} (>= 0)")
+    audio = f32c(audio)
+    if audio.dim() != 2:
+        raise ValueError(f"audio_edges: audio {tuple(audio.shape)}, expected [S, L]")
+    S, L = audio.shape
+    lens = _lens32(lengths, S, audio.device)
+    start = torch.empty((S,), dtype=torch.int32, device=audio.device)
+    end = torch.empty((S,), dtype=torch.int32, device=audio.device)
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_audio_edges_workspace_bytes(S, L), audio.device)
+    check(L_.mt_audio_edges(ptr(audio), S, L, ptr(lens), thr, pad, ptr(start), ptr(end), ws.data_ptr(), ws.numel(),
+                            stream_handle(audio.device)), "audio_edges")
+    return start, end
+
+
+def join_plan(doc_first: torch.Tensor, start: torch.Tensor, end: torch.Tensor, gap: torch.Tensor, head: int,
+              tail: int, L: int, Lcap: int = 1 << 30):
+    """doc_first int32 [D + 1] (CSR), start / end / gap int32 [S], all on the device -> (dst int32 [S], doc_len
+    int32 [D], bad int32 [1]): join.plan_ref (mt_join_plan). Nothing comes back to the host."""
+    require_gpu(doc_first, start, end, gap, what="join_plan")
+    head, tail, L, Lcap = int(head), int(tail), int(L), int(Lcap)
+    if head < 0 or tail < 0:
+        raise ValueError(f"join_plan: head {head} and tail {tail} are sample counts >= 0")
+    S, D = int(start.shape[0]), int(doc_first.shape[0]) - 1
+    if not (1 <= S <= JOIN_MAX_ROWS and 1 <= D <= JOIN_MAX_ROWS):
+        raise ValueError(f"join_plan: {S} segments in {D} documents (1..{JOIN_MAX_ROWS} each)")
+    dev = start.device
+    _table(doc_first, D + 1, dev, "join_plan: doc_first")
+    for t in (start, end, gap):
+        _table(t, S, dev, "join_plan")
+    dst = torch.zeros((S,), dtype=torch.int32, device=dev)
+    doc_len = torch.empty((max(D, 0),), dtype=torch.int32, device=dev)
+    bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    check(lib().mt_join_plan(ptr(doc_first), D, ptr(start), ptr(end), ptr(gap), S, L, head, tail, Lcap, ptr(dst),
+                             ptr(doc_len), ptr(bad), stream_handle(dev)), "join_plan")
+    return dst, doc_len, bad
+
+
+def join(seg: torch.Tensor, start: torch.Tensor, end: torch.Tensor, doc_first: torch.Tensor, dst: torch.Tensor,
+         doc_len: torch.Tensor, fade: int, bad: Optional[torch.Tensor] = None, Ld: Optional[int] = None):
+    """seg fp32 [S, L] (read in place), the tables of audio_edges / join_plan -> out fp32 [D, Ld]: join.join_ref
+    (mt_join). Ld = max(doc_len) (at least 1) unless given; it and join_plan's `bad` flag come to the host in one
+    device -> host copy, the one synchronisation of the chain. ValueError when `bad` is set (a document longer than
+    join_plan's Lcap)."""
+    require_gpu(seg, what="join")
+    if seg.dtype != torch.float32 or not seg.is_contiguous() or seg.dim() != 2:
+        raise ValueError("join: seg is a contiguous fp32 [S, L] tensor")
+    S, L = seg.shape
+    D = int(doc_first.shape[0]) - 1
+    if not (1 <= S <= JOIN_MAX_ROWS and 1 <= D <= JOIN_MAX_ROWS):
+        raise ValueError(f"join: {S} segments in {D} documents (1..{JOIN_MAX_ROWS} each)")
+    dev = seg.device
+    fade = int(fade)
+    table = _ramp_table(fade, dev)
+    _table(doc_first, D + 1, dev, "join: doc_first")
+    for t in (start, end, dst):
+        _table(t, S, dev, "join")
+    _table(doc_len, D, dev, "join: doc_len")
+    if bad is not None or Ld is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=dev) if bad is None else bad.reshape(1)
+        longest, is_bad = torch.cat([doc_len.max().reshape(1), flag]).cpu().tolist()
+        if is_bad:
+            raise ValueError("join: a document is longer than the plan's Lcap samples")
+        Ld = max(int(longest), 1) if Ld is None else int(Ld)
+    out = torch.empty((D, int(Ld)), dtype=torch.float32, device=dev)
+    check(lib().mt_join(ptr(seg), S, L, ptr(start), ptr(end), ptr(doc_first), D, ptr(dst), ptr(doc_len), ptr(table),
+                        fade, ptr(out), int(Ld), stream_handle(dev)), "join")
+    return out
+
+
 def maximum_path(neg_cent: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """train_standalone.py:280-325 on the GPU: neg_cent [B,Tx,Ty], attention mask [B,Tx,Ty] (x_mask x
     y_mask) -> one-hot monotonic path [B,Tx,Ty] in neg_cent's dtype. The lengths are the mask's row /
