@@ -19,6 +19,7 @@
  *   mt_resample, mt_audio_stats, <- the host steps after the vocoder, main.py:198-201 (`.clamp(-1, 1)`, soundfile's
  *   mt_audio_encode                 PCM16 write), plus rate conversion and level, which the reference leaves to callers
  *   mt_loudness, mt_true_peak    <- no counterpart: BS.1770 loudness and true peak of the output, for delivery levels
+ *   mt_peak_envelope, mt_limit   <- no counterpart: look-ahead true-peak limiter, so that both figures are met
  *   mt_window_gather,            <- streaming delivery of the steps above (windows of the mel / the audio, the outputs
  *   mt_window_scatter,              that became final): no counterpart in the reference, which vocodes whole utterances
  *   mt_resample_range
@@ -409,6 +410,34 @@ int mt_loudness(const float* audio, int B, int L, const int32_t* lens, const dou
 size_t mt_true_peak_workspace_bytes(int B, int L);
 int mt_true_peak(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase, int half,
                  const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, void* stream);
+/* Look-ahead true-peak limiter (matcha_hip/limiter.py is the specification on the CPU, bit for bit).
+ * lens as in mt_audio_stats; a row's results depend on its valid samples alone. Neither entry point allocates on the
+ * device or uses atomics; every argument error is refused before any launch. 1 <= B <= 65535, L as mt_true_peak.
+ *
+ * mt_peak_envelope: env[b][i] (fp32 [B][L], zero from len_b on) = max(|x[i]|, max |r[m]|, 4i - 3 <= m <= 4i + 3 inside
+ * [0, 4 len_b)), r the 4x oversampled row exactly as mt_true_peak forms it (same table, same chain; nothing of r is
+ * written). The maximum starts at 0 and is taken with fmaxf: a NaN counts as absent. env must not overlap audio.
+ * Workspace: mt_peak_envelope_workspace_bytes (a constant), 16-byte aligned.
+ *
+ * mt_limit: the row's gain g = float32(double(g_in) level / sqrt(meansq[b])) with g_in = gain_in[b] (fp32 [B], device;
+ * NULL: 1), formed on the device by the encoder's own gain routine; g = g_in where peak[b] == 0 or meansq[b] == 0.
+ * peak (fp32 [B]) only tells whether the row is levelled at all: peak[b] == 0 leaves it untouched (s = 1). With
+ * c32 = float32(ceiling) (ceiling: a linear amplitude, finite and positive, as is level):
+ *   a = fl32(g env[b][i]);  r = c32 / a (IEEE fp32) where a > c32, else 1;  q[i] = floor(r 2^30), 2^30 outside the row
+ *   m[j] = min q[j .. j + W - 1];  S[i] = sum_{k < W} m[i - k];  s[i] = float32(double(S[i]) / double(W 2^30))
+ *   out[b][i] = fl32(fl32(g audio[b][i]) s[i]), two products rounded separately; zero from len_b on.
+ * s[i] <= r[i] at every sample: no sample's envelope passes the ceiling. The gain falls over W samples before a peak
+ * and recovers over W after it (1 <= W <= 2048). reduction[b] (fp32 [B]) = min_i s[i] (1 for an empty row),
+ * gain_out[b] (fp32 [B]) = g. Integer minimum (van Herk / Gil-Werman blocks of W) and integer sum: the same bits in
+ * any order. out must overlap neither audio nor env. Workspace: mt_limit_workspace_bytes (0 and mt_last_error for a
+ * refused shape or window), 16-byte aligned. */
+size_t mt_peak_envelope_workspace_bytes(void);
+int mt_peak_envelope(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase, int half,
+                     float* env, void* ws, size_t ws_bytes, void* stream);
+size_t mt_limit_workspace_bytes(int B, int L, int W);
+int mt_limit(const float* audio, const float* env, int B, int L, const int32_t* lens, const float* peak,
+             const double* meansq, const float* gain_in, double level, double ceiling, int W, float* out,
+             float* reduction, float* gain_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Streaming delivery (matcha_hip/stream_plan.py is the specification of the windows): cut one window

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "mt_common.h"
+#include "mt_level.h"     // NORM_*, gain_of (shared with mt_limiter.hip)
 #include "mt_resample.h"  // the tile's staging and FMA chain, utt_len
 
 namespace mt {
@@ -140,17 +141,7 @@ __global__ __launch_bounds__(256) void audio_stats_final_kernel(const double* __
   }
 }
 
-enum { NORM_NONE = 0, NORM_PEAK = 1, NORM_RMS = 2 };
 enum { ENC_F32 = 0, ENC_PCM16 = 1, ENC_MULAW = 2 };
-
-// audio_out.gain_ref
-__device__ __forceinline__ float gain_of(float peak, double meansq, int normalize, double level, int limit) {
-  if (normalize == NORM_NONE || !(peak > 0.f)) return 1.f;
-  if (normalize == NORM_PEAK) return (float)(level / (double)peak);
-  double g = level / sqrt(meansq);
-  if (limit) g = fmin(g, 1.0 / (double)peak);
-  return (float)g;
-}
 
 // audio_out.mulaw_ref
 __device__ __forceinline__ unsigned mulaw_of(int q) {

@@ -41,6 +41,14 @@ int loudness(const float* audio, int B, int L, const int* lens, const double* co
 size_t true_peak_workspace_bytes(int B, int L);
 int true_peak(const float* audio, int B, int L, const int* lens, const float* taps, int half,
               const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, hipStream_t st);
+// mt_limiter.hip
+size_t peak_envelope_workspace_bytes();
+int peak_envelope(const float* audio, int B, int L, const int* lens, const float* taps, int half, float* env, void* ws,
+                  size_t ws_bytes, hipStream_t st);
+size_t limit_workspace_bytes(int B, int L, int W);
+int limit(const float* audio, const float* env, int B, int L, const int* lens, const float* peak,
+          const double* meansq, const float* gain_in, double level, double ceiling, int W, float* out,
+          float* reduction, float* gain_out, void* ws, size_t ws_bytes, hipStream_t st);
 // mt_stream.hip
 int window_gather(const float* src, int Bs, int C, int Ls, const int* row_src, const int* row_start,
                   const int* row_len, int R, int W, float* rows, hipStream_t st);
@@ -481,6 +489,20 @@ int mt_true_peak(const float* audio, int B, int L, const int32_t* lens, const fl
                  const float* sample_peak, float* tpeak, void* ws, size_t ws_bytes, void* stream) {
   return mt::true_peak(audio, B, L, lens, taps_polyphase, half, sample_peak, tpeak, ws, ws_bytes,
                        (hipStream_t)stream);
+}
+
+// ---- look-ahead true-peak limiter ----
+size_t mt_peak_envelope_workspace_bytes(void) { return mt::peak_envelope_workspace_bytes(); }
+int mt_peak_envelope(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase, int half,
+                     float* env, void* ws, size_t ws_bytes, void* stream) {
+  return mt::peak_envelope(audio, B, L, lens, taps_polyphase, half, env, ws, ws_bytes, (hipStream_t)stream);
+}
+size_t mt_limit_workspace_bytes(int B, int L, int W) { return mt::limit_workspace_bytes(B, L, W); }
+int mt_limit(const float* audio, const float* env, int B, int L, const int32_t* lens, const float* peak,
+             const double* meansq, const float* gain_in, double level, double ceiling, int W, float* out,
+             float* reduction, float* gain_out, void* ws, size_t ws_bytes, void* stream) {
+  return mt::limit(audio, env, B, L, lens, peak, meansq, gain_in, level, ceiling, W, out, reduction, gain_out, ws,
+                   ws_bytes, (hipStream_t)stream);
 }
 
 // ---- streaming delivery: window gather / scatter ----

@@ -16,6 +16,13 @@ specification on the CPU).
 levels every utterance to -16 LUFS (ITU-R BS.1770 gated loudness) with its true peak held at or under -1 dBTP
 (mt_loudness and mt_true_peak in place of mt_audio_stats; DESIGN.md §21, matcha_hip/loudness.py), and
 `AudioOutput(16000).measure(wav, lengths)` reports both figures of what the stage would deliver at gain 1.
+
+    out = AudioOutput(16000, loudness=-16.0, true_peak=-1.0, limiter=5.0, encoding="pcm16")(wav, lengths)
+
+meets both figures where they conflict: a look-ahead limiter turns the gain down around the peaks only (over 5 ms
+before and after each) and the level is made up until the limited signal reads the target (mt_peak_envelope and
+mt_limit; DESIGN.md §23, matcha_hip/limiter.py). `AudioOutput.limited` returns that signal before encoding, with the
+gain, the deepest reduction and the last static trim of every row.
 """
 from __future__ import annotations
 
@@ -25,6 +32,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from matcha_hip import audio_out
+from matcha_hip import limiter as lm
 from matcha_hip import loudness as ld
 from matcha_hip import runtime as rt
 
@@ -43,6 +51,15 @@ class Loudness(NamedTuple):
     sample_rate: int
 
 
+class Limited(NamedTuple):
+    audio: torch.Tensor          # [B, L] fp32 at sample_rate: the levelled and limited signal, before trim and encoding
+    lengths: torch.Tensor        # int32 [B]
+    sample_rate: int
+    gain: torch.Tensor           # fp32 [B], the make-up gain of the last pass
+    reduction: torch.Tensor      # fp32 [B], the smallest factor the limiter applied on top of it (1: never worked)
+    trim: torch.Tensor           # fp32 [B], min(1, ceiling / ((1 + eps) true peak of `audio`)): the encoder's gain
+
+
 class AudioOutput:
     """sample_rate / source_rate: any pair whose reduced factor up/down has both parts <= 1024 (from 22,050 Hz: 8000,
     11025, 16000, 24000, 32000, 44100, 48000, ...), Kaiser-windowed sinc with `zeros` zero crossings per side at the
@@ -51,11 +68,15 @@ class AudioOutput:
     stops where the peak would pass full scale). encoding: "f32", "pcm16" or "mulaw" (G.711). Level and encoding are
     measured on, and applied to, the resampled signal. loudness: a target in LUFS (-70 < target <= 0, ITU-R BS.1770
     gated loudness; needs normalize=None and sample_rate >= 8000): the row's loudness becomes the target, and with
-    `limit` the gain stops where the row's true peak (4x oversampled) would pass `true_peak` dBTP (<= 0)."""
+    `limit` the gain stops where the row's true peak (4x oversampled) would pass `true_peak` dBTP (<= 0).
+    limiter: a window in ms (needs loudness=; 1 .. 2048 samples at sample_rate): instead of capping the whole row's
+    gain, the gain is turned down around the peaks alone, falling over one window before a peak and recovering over
+    one after it, and made up in `limiter_passes` (1 .. 8) rounds so that the limited row reads the target."""
 
     def __init__(self, sample_rate: int = 22050, source_rate: int = 22050, normalize: Optional[str] = None,
                  level: Optional[float] = None, limit: bool = True, encoding: str = "f32", zeros: int = 10,
-                 beta: float = 5.0, hop: int = 256, loudness: Optional[float] = None, true_peak: float = -1.0):
+                 beta: float = 5.0, hop: int = 256, loudness: Optional[float] = None, true_peak: float = -1.0,
+                 limiter: Optional[float] = None, limiter_passes: int = 3):
         if normalize not in rt.NORMALIZE_CODES:
             raise ValueError(f"normalize must be one of {list(rt.NORMALIZE_CODES)}, got {normalize!r}")
         if encoding not in rt.ENCODING_CODES:
@@ -80,6 +101,14 @@ class AudioOutput:
                 raise ValueError(f"loudness: sample_rate {self.sample_rate} is below {ld.MIN_RATE} Hz, the lowest "
                                  "rate the K-weighting is designed for")
         self.loudness, self.true_peak = loudness, true_peak
+        self.limiter, self.limiter_window, self.limiter_passes = None, None, int(limiter_passes)
+        if not 1 <= self.limiter_passes <= lm.MAX_PASSES or self.limiter_passes != limiter_passes:
+            raise ValueError(f"limiter_passes must be an integer in 1 .. {lm.MAX_PASSES}, got {limiter_passes}")
+        if limiter is not None:
+            if loudness is None:
+                raise ValueError(f"limiter={limiter} makes up the level to a loudness target: set loudness=")
+            self.limiter = float(limiter)
+            self.limiter_window = lm.window_samples(self.sample_rate, self.limiter)  # ValueError outside 1 .. 2048
 
     def _resampled(self, audio: torch.Tensor, lengths, what: str):
         """-> (audio [B, L_out] at sample_rate, lens int32 [B] in samples)"""
@@ -129,6 +158,13 @@ class AudioOutput:
         if audio.dim() != 2:
             raise ValueError(f"AudioOutput.finish: audio {tuple(audio.shape)}, expected [B, L]")
         lens = lens_samples
+        if self.limiter is not None:
+            # the limited signal through the unchanged encoder: "rms" at mean square 1 and level 1 is gain 1, which
+            # the limit caps at 1 / peak = ceiling / ((1 + eps) TP'): the trim
+            lim, peak_eff = self._limited(audio, lens)
+            out, _ = rt.encode_audio(lim.audio, lens, "rms", 1.0, True, self.encoding,
+                                     stats=(peak_eff, torch.ones_like(peak_eff, dtype=torch.float64)))
+            return AudioOut(out, lens, self.sample_rate, lim.gain * lim.trim)
         if self.loudness is None:
             out, gain = rt.encode_audio(audio, lens, self.normalize, self.level, self.limit, self.encoding)
             return AudioOut(out, lens, self.sample_rate, gain)
@@ -140,3 +176,38 @@ class AudioOutput:
         out, gain = rt.encode_audio(audio, lens, "rms", ld.target_level(self.loudness), self.limit, self.encoding,
                                     stats=(peak_eff, energy))
         return AudioOut(out, lens, self.sample_rate, gain)
+
+    def _limited(self, audio: torch.Tensor, lens: torch.Tensor):
+        """-> (Limited, peak_eff fp32 [B] = TP' (1 + eps) / ceiling of the limited rows, 0 for a row that was not
+        levelled)"""
+        c = 10.0 ** (self.true_peak / 20.0)
+        level = ld.target_level(self.loudness)
+        energy, tp = self._measure(audio, lens)
+        live = energy > 0
+        zero = torch.zeros_like(tp)
+        peak0 = torch.where(live, (tp.double() / c).float(), zero)
+        plan4 = rt.resample_plan(self.sample_rate, 4 * self.sample_rate, self.zeros, self.beta, audio.device)
+        env = rt.peak_envelope(audio, lens, plan4)
+        gain, e_k = None, energy
+        for k in range(self.limiter_passes):
+            y, gain, reduction = rt.limit(audio, env, lens, (peak0, e_k), level, c, self.limiter_window, gain_in=gain)
+            if k + 1 < self.limiter_passes:
+                e_k, _ = rt.loudness(y, lens, self.sample_rate)
+        # limiter.trim_peak_ref: TP' over the ceiling with the headroom that fp32 delivery and the meter's chain need
+        headroom = 1.0 + lm.trim_headroom(plan4.taps_host)
+        peak_eff = torch.where(live, (rt.true_peak(y, lens, plan4).double() / c * headroom).float(), zero)
+        # audio_out.gain_ref("rms", meansq 1, level 1, limit): min(1, 1 / peak) in fp64, rounded to fp32
+        trim = torch.where(peak_eff > 0, 1.0 / peak_eff.double(), torch.ones_like(energy)).clamp_(max=1.0).float()
+        return Limited(y, lens, self.sample_rate, gain, reduction, trim), peak_eff
+
+    @torch.inference_mode()
+    def limited(self, audio: torch.Tensor, lens_samples: torch.Tensor) -> Limited:
+        """audio fp32 [B, L] already at sample_rate, lens_samples int32 [B] in samples (as finish takes them) -> the
+        levelled and limited rows before trim and encoding, and the report (limiter.limiter_ref per row). Needs
+        limiter=. No host synchronisation: the gains, energies and peaks stay on the device."""
+        if self.limiter is None:
+            raise ValueError("AudioOutput.limited: the stage was built without limiter=")
+        rt.require_gpu(audio, what="AudioOutput.limited")
+        if audio.dim() != 2:
+            raise ValueError(f"AudioOutput.limited: audio {tuple(audio.shape)}, expected [B, L]")
+        return self._limited(audio, lens_samples)[0]

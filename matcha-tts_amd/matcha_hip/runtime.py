@@ -999,6 +999,70 @@ def true_peak(audio: torch.Tensor, lengths, plan4: ResamplePlan) -> torch.Tensor
     return tpeak
 
 
+# ---- look-ahead true-peak limiter (limiter.py is the specification) ------------------------------
+
+# samples per workgroup of peak_envelope_kernel and of limit_kernel (mt_limiter.hip LM_ENV_T, LM_T) and the widest
+# smoothing window (LM_MAX_W): tests put row ends and peaks around the tiles' edges
+ENVELOPE_TILE = 512
+LIMIT_TILE = 2048
+LIMIT_MAX_WINDOW = 2048
+
+
+def peak_envelope(audio: torch.Tensor, lengths, plan4: ResamplePlan) -> torch.Tensor:
+    """audio [B, L], lengths in samples (int [B], or None = L), plan4 = resample_plan(fs, 4 fs) -> env fp32 [B, L]:
+    limiter.envelope_ref of every row, zero from its length on (mt_peak_envelope). The 4x signal has the bits of
+    true_peak's and is never written."""
+    require_gpu(audio, what="peak_envelope")
+    if (plan4.up, plan4.down) != (4, 1):
+        raise ValueError(f"peak_envelope: the plan is {plan4.up}/{plan4.down}; the envelope is taken at 4/1")
+    audio = f32c(audio)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    env = torch.empty((B, L), dtype=torch.float32, device=audio.device)
+    L_ = lib()
+    taps = plan4.taps if plan4.taps.device == audio.device else plan4.taps.to(audio.device)
+    ws = _Workspace.get(L_.mt_peak_envelope_workspace_bytes(), audio.device)
+    check(L_.mt_peak_envelope(ptr(audio), B, L, ptr(lens), ptr(taps), plan4.half, ptr(env), ws.data_ptr(), ws.numel(),
+                              stream_handle(audio.device)), "peak_envelope")
+    return env
+
+
+def limit(audio: torch.Tensor, env: torch.Tensor, lengths, stats, level: float, ceiling: float, W: int,
+          gain_in: Optional[torch.Tensor] = None):
+    """audio, env [B, L] (env = peak_envelope(audio, ...)), lengths in samples, stats = (peak fp32 [B], meansq fp64
+    [B]) on the device -> (y fp32 [B, L], gain fp32 [B], reduction fp32 [B]) (mt_limit): gain =
+    float32(double(gain_in) level / sqrt(meansq)) (gain_in: fp32 [B], None = 1; unchanged where peak == 0 or meansq ==
+    0), y = limiter.apply_ref(x, gain, limiter.gain_curve_ref(env, gain, float32(ceiling), W)), untouched rows (peak
+    == 0) at s = 1, reduction = min s. ceiling: a linear amplitude, 10^(dBTP / 20); W: the window in samples."""
+    require_gpu(audio, what="limit")
+    level, ceiling, W = float(level), float(ceiling), int(W)
+    if not (0.0 < level < float("inf")) or not (0.0 < ceiling < float("inf")):
+        raise ValueError(f"limit: level {level} and ceiling {ceiling} must be finite and positive")
+    if not 1 <= W <= LIMIT_MAX_WINDOW:
+        raise ValueError(f"limit: window of {W} samples outside 1 .. {LIMIT_MAX_WINDOW}")
+    audio, env = f32c(audio), f32c(env)
+    if audio.dim() != 2 or env.shape != audio.shape:
+        raise ValueError(f"limit: audio {tuple(audio.shape)} and env {tuple(env.shape)}, expected equal [B, L]")
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    peak, meansq = stats
+    if peak.shape != (B,) or peak.dtype != torch.float32 or meansq.shape != (B,) or meansq.dtype != torch.float64:
+        raise ValueError(f"limit: stats are (peak fp32 [{B}], meansq fp64 [{B}])")
+    if gain_in is not None and (gain_in.shape != (B,) or gain_in.dtype != torch.float32):
+        raise ValueError(f"limit: gain_in is fp32 [{B}]")
+    peak, meansq = peak.contiguous(), meansq.contiguous()
+    gain_in = None if gain_in is None else gain_in.contiguous()
+    y = torch.empty((B, L), dtype=torch.float32, device=audio.device)
+    gain = torch.empty((B,), dtype=torch.float32, device=audio.device)
+    reduction = torch.empty((B,), dtype=torch.float32, device=audio.device)
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_limit_workspace_bytes(B, L, W), audio.device)
+    check(L_.mt_limit(ptr(audio), ptr(env), B, L, ptr(lens), ptr(peak), ptr(meansq), ptr(gain_in), level, ceiling, W,
+                      ptr(y), ptr(reduction), ptr(gain), ws.data_ptr(), ws.numel(), stream_handle(audio.device)),
+          "limit")
+    return y, gain, reduction
+
+
 def resample_range(audio: torch.Tensor, plan: ResamplePlan, lengths, lmul: int, m_lo: int, cnt: int,
                    out: Optional[torch.Tensor] = None):
     """The outputs [m_lo, m_lo + cnt) of ``resample``'s rows -> (out fp32 [B, cnt], out_cnt int32 [B]), bit for bit,

@@ -4,7 +4,8 @@
 
 B utterances at synthetic.ljspeech_lengths (mel frames, x 256 samples) in one padded [B, L] buffer of noise; each
 iteration runs the ragged denoiser (the stage this one follows, for comparison) and AudioOutput(rate, "peak", "pcm16");
-with --loudness LUFS also AudioOutput(rate, loudness=LUFS) (the K-weighting scan and the true peak).
+with --loudness LUFS also AudioOutput(rate, loudness=LUFS) (the K-weighting scan and the true peak),
+and with --limiter MS also AudioOutput(rate, loudness=LUFS or -16, limiter=MS) (the look-ahead limiter).
 Prints one JSON line: the shapes, and the bytes each launch has to move with their time at the HBM rate DESIGN.md §4
 uses. Kernel times come from the trace, not from this script.
 """
@@ -31,6 +32,8 @@ def main():
     p.add_argument("--encoding", default="pcm16")
     p.add_argument("--loudness", type=float, default=None,
                    help="also run AudioOutput(rate, loudness=LUFS) on the same batch each iteration (DESIGN.md §21)")
+    p.add_argument("--limiter", type=float, default=None,
+                   help="also run AudioOutput(rate, loudness=LUFS or -16, limiter=MS) each iteration (DESIGN.md §23)")
     a = p.parse_args()
     from hifigan.output import AudioOutput
     from matcha_hip import audio_out, synthetic
@@ -44,11 +47,15 @@ def main():
     bias = torch.rand(513, generator=g).to(dev)
     stage = AudioOutput(a.rate, normalize="peak", encoding=a.encoding)
     leveled = None if a.loudness is None else AudioOutput(a.rate, loudness=a.loudness, encoding=a.encoding)
+    limited = None if a.limiter is None else AudioOutput(
+        a.rate, loudness=-16.0 if a.loudness is None else a.loudness, limiter=a.limiter, encoding=a.encoding)
     for _ in range(a.warmup + a.iters):
         d = rt.denoise(audio, bias, 0.00025, lengths=ld)
         out = stage(d, ld)
         if leveled is not None:
             leveled(d, ld)
+        if limited is not None:
+            limited(d, ld)
     torch.cuda.synchronize()
     up, down = audio_out.rates(22050, a.rate)
     n_in = int(256 * lens.sum())
@@ -58,6 +65,9 @@ def main():
     moved = {"resample_kernel": 4 * n_in + 4 * a.batch * Lout,           # valid samples in, whole rows out
              "audio_stats_kernel": 4 * n_out,
              "audio_encode_kernel": (4 + esz) * a.batch * Lout}
+    if limited is not None:  # per launch: samples in and envelope out; samples and envelope in, whole rows out
+        moved["peak_envelope_kernel"] = 4 * n_out + 4 * a.batch * Lout
+        moved["limit_kernel"] = 8 * n_out + 4 * a.batch * Lout
     print(json.dumps({"rate": a.rate, "up": up, "down": down, "batch": a.batch, "L": L, "Lout": Lout,
                       "samples_in": n_in, "samples_out": n_out, "iters": a.warmup + a.iters,
                       "bytes": moved, "hbm_us": {k: round(v / HBM * 1e6, 2) for k, v in moved.items()}}))
