@@ -22,7 +22,9 @@
  *   mt_peak_envelope, mt_limit   <- no counterpart: look-ahead true-peak limiter, so that both figures are met
  *   mt_window_gather,            <- streaming delivery of the steps above (windows of the mel / the audio, the outputs
  *   mt_window_scatter,              that became final): no counterpart in the reference, which vocodes whole utterances
- *   mt_resample_range
+ *   mt_resample_range,
+ *   mt_peak_envelope_range,      <- a fixed gain and the limiter chunk by chunk: ranges of mt_peak_envelope's and
+ *   mt_limit_range                  mt_limit's rows, read in place from buffers that are still being filled
  *   mt_audio_edges, mt_join_plan, <- long-form synthesis: a batch of sentences joined into documents (trim, pauses,
  *   mt_join                         crossfades); no counterpart in the reference, which writes one file per sentence
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
@@ -438,6 +440,30 @@ size_t mt_limit_workspace_bytes(int B, int L, int W);
 int mt_limit(const float* audio, const float* env, int B, int L, const int32_t* lens, const float* peak,
              const double* meansq, const float* gain_in, double level, double ceiling, int W, float* out,
              float* reduction, float* gain_out, void* ws, size_t ws_bytes, void* stream);
+/* Ranges of the two, for a stream at a gain fixed beforehand: the tile bodies of mt_peak_envelope and
+ * mt_limit run from i_lo instead of from 0, on full-length buffers [B][L] read in place. lens are the rows' FINAL
+ * lengths; what happens at a row's end is the whole-row kernel's. i_lo >= 0, cnt >= 1, i_lo + cnt < 2^31 - 8192; a
+ * range may lie past the end of a row or of L. Every argument error is refused before any launch; no device
+ * allocation, no atomics.
+ *
+ * mt_peak_envelope_range: writes env[b][i] for i in [i_lo, i_lo + cnt) inside [0, len_b) with the bits of
+ * mt_peak_envelope, and nothing else of env (fp32 [B][L], the same buffer across calls). Of audio[b] it reads no
+ * sample past min(len_b - 1, i_lo + cnt - 1 + (half + 3) / 4): later samples need not be written yet. Workspace as
+ * mt_peak_envelope.
+ *
+ * mt_limit_range: out[b][j] (fp32 [B][cnt]) has the bits of mt_limit's out[b][i_lo + j] called with peak = 1,
+ * meansq = 1, level = 1 and gain_in = gain, which makes g = gain[b] (fp32 [B], device) as it stands; zero from the
+ * row's end on. out_cnt[b] (int32 [B]) = clamp(len_b - i_lo, 0, cnt). Of env[b] it reads only
+ * [i_lo - (W - 1), i_lo + cnt + W - 2] inside [0, len_b), 2^30 in place of q outside the row; of audio[b] only the
+ * range. reduction (fp32 [B]) is read and written: min(its value, min s over the range), from per-tile minima in the
+ * workspace and a final kernel; the caller starts it at 1. out must overlap neither audio nor env. Workspace:
+ * mt_limit_range_workspace_bytes (0 and mt_last_error for a refused shape or window), 16-byte aligned. */
+int mt_peak_envelope_range(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase,
+                           int half, int i_lo, int cnt, float* env, void* ws, size_t ws_bytes, void* stream);
+size_t mt_limit_range_workspace_bytes(int B, int cnt, int W);
+int mt_limit_range(const float* audio, const float* env, int B, int L, const int32_t* lens, const float* gain,
+                   double ceiling, int W, int i_lo, int cnt, float* out, int32_t* out_cnt, float* reduction, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Streaming delivery (matcha_hip/stream_plan.py is the specification of the windows): cut one window

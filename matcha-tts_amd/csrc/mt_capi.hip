@@ -49,6 +49,12 @@ size_t limit_workspace_bytes(int B, int L, int W);
 int limit(const float* audio, const float* env, int B, int L, const int* lens, const float* peak,
           const double* meansq, const float* gain_in, double level, double ceiling, int W, float* out,
           float* reduction, float* gain_out, void* ws, size_t ws_bytes, hipStream_t st);
+int peak_envelope_range(const float* audio, int B, int L, const int* lens, const float* taps, int half, int i_lo,
+                        int cnt, float* env, void* ws, size_t ws_bytes, hipStream_t st);
+size_t limit_range_workspace_bytes(int B, int cnt, int W);
+int limit_range(const float* audio, const float* env, int B, int L, const int* lens, const float* gain,
+                double ceiling, int W, int i_lo, int cnt, float* out, int* out_cnt, float* reduction, void* ws,
+                size_t ws_bytes, hipStream_t st);
 // mt_stream.hip
 int window_gather(const float* src, int Bs, int C, int Ls, const int* row_src, const int* row_start,
                   const int* row_len, int R, int W, float* rows, hipStream_t st);
@@ -503,6 +509,18 @@ int mt_limit(const float* audio, const float* env, int B, int L, const int32_t* 
              float* reduction, float* gain_out, void* ws, size_t ws_bytes, void* stream) {
   return mt::limit(audio, env, B, L, lens, peak, meansq, gain_in, level, ceiling, W, out, reduction, gain_out, ws,
                    ws_bytes, (hipStream_t)stream);
+}
+int mt_peak_envelope_range(const float* audio, int B, int L, const int32_t* lens, const float* taps_polyphase,
+                           int half, int i_lo, int cnt, float* env, void* ws, size_t ws_bytes, void* stream) {
+  return mt::peak_envelope_range(audio, B, L, lens, taps_polyphase, half, i_lo, cnt, env, ws, ws_bytes,
+                                 (hipStream_t)stream);
+}
+size_t mt_limit_range_workspace_bytes(int B, int cnt, int W) { return mt::limit_range_workspace_bytes(B, cnt, W); }
+int mt_limit_range(const float* audio, const float* env, int B, int L, const int32_t* lens, const float* gain,
+                   double ceiling, int W, int i_lo, int cnt, float* out, int32_t* out_cnt, float* reduction, void* ws,
+                   size_t ws_bytes, void* stream) {
+  return mt::limit_range(audio, env, B, L, lens, gain, ceiling, W, i_lo, cnt, out, out_cnt, reduction, ws, ws_bytes,
+                         (hipStream_t)stream);
 }
 
 // ---- streaming delivery: window gather / scatter ----

@@ -23,6 +23,12 @@ meets both figures where they conflict: a look-ahead limiter turns the gain down
 before and after each) and the level is made up until the limited signal reads the target (mt_peak_envelope and
 mt_limit; DESIGN.md §23, matcha_hip/limiter.py). `AudioOutput.limited` returns that signal before encoding, with the
 gain, the deepest reduction and the last static trim of every row.
+
+    out = AudioOutput(16000, gain_db=6.0, true_peak=-1.0, limiter=5.0, encoding="pcm16")(wav, lengths)
+
+applies a gain fixed beforehand (calibrated per voice, say, from `measure`) and the same limiter in one pass: nothing
+of it needs the whole utterance, so hifigan.stream.WaveStreamer delivers exactly this chunk by chunk (DESIGN.md §24,
+limiter.limit_fixed_ref). `gain_db=` of a call overrides the stage's figure row by row.
 """
 from __future__ import annotations
 
@@ -71,12 +77,16 @@ class AudioOutput:
     `limit` the gain stops where the row's true peak (4x oversampled) would pass `true_peak` dBTP (<= 0).
     limiter: a window in ms (needs loudness=; 1 .. 2048 samples at sample_rate): instead of capping the whole row's
     gain, the gain is turned down around the peaks alone, falling over one window before a peak and recovering over
-    one after it, and made up in `limiter_passes` (1 .. 8) rounds so that the limited row reads the target."""
+    one after it, and made up in `limiter_passes` (1 .. 8) rounds so that the limited row reads the target.
+    gain_db: a fixed gain in dB (finite; excludes normalize= and loudness=): every row is multiplied by
+    float32(10^(gain_db / 20)), nothing is measured. With limiter= the gain is turned down around the peaks as above,
+    in one pass: no make-up and no trim, and `limiter_passes` is ignored; every sample's envelope is held at the
+    ceiling, the delivered true peak passes it by what the smoothing lets through."""
 
     def __init__(self, sample_rate: int = 22050, source_rate: int = 22050, normalize: Optional[str] = None,
                  level: Optional[float] = None, limit: bool = True, encoding: str = "f32", zeros: int = 10,
                  beta: float = 5.0, hop: int = 256, loudness: Optional[float] = None, true_peak: float = -1.0,
-                 limiter: Optional[float] = None, limiter_passes: int = 3):
+                 limiter: Optional[float] = None, limiter_passes: int = 3, gain_db: Optional[float] = None):
         if normalize not in rt.NORMALIZE_CODES:
             raise ValueError(f"normalize must be one of {list(rt.NORMALIZE_CODES)}, got {normalize!r}")
         if encoding not in rt.ENCODING_CODES:
@@ -100,13 +110,19 @@ class AudioOutput:
             if self.sample_rate < ld.MIN_RATE:
                 raise ValueError(f"loudness: sample_rate {self.sample_rate} is below {ld.MIN_RATE} Hz, the lowest "
                                  "rate the K-weighting is designed for")
-        self.loudness, self.true_peak = loudness, true_peak
+        if gain_db is not None:
+            if normalize is not None or loudness is not None:
+                raise ValueError(f"gain_db={gain_db} fixes the gain; normalize= and loudness= measure one: use one")
+            lm.fixed_gain_ref(gain_db)  # ValueError unless finite
+            gain_db = float(gain_db)
+        self.loudness, self.true_peak, self.gain_db = loudness, true_peak, gain_db
         self.limiter, self.limiter_window, self.limiter_passes = None, None, int(limiter_passes)
         if not 1 <= self.limiter_passes <= lm.MAX_PASSES or self.limiter_passes != limiter_passes:
             raise ValueError(f"limiter_passes must be an integer in 1 .. {lm.MAX_PASSES}, got {limiter_passes}")
         if limiter is not None:
-            if loudness is None:
-                raise ValueError(f"limiter={limiter} makes up the level to a loudness target: set loudness=")
+            if loudness is None and gain_db is None:
+                raise ValueError(f"limiter={limiter} limits a levelled signal: set loudness= (the level is made up "
+                                 "to the target) or gain_db= (a fixed gain)")
             self.limiter = float(limiter)
             self.limiter_window = lm.window_samples(self.sample_rate, self.limiter)  # ValueError outside 1 .. 2048
 
@@ -143,21 +159,55 @@ class AudioOutput:
         energy, tp = self._measure(audio, lens)
         return Loudness(10.0 * torch.log10(energy) - 0.691, 20.0 * torch.log10(tp.double()), lens, self.sample_rate)
 
-    @torch.inference_mode()
-    def __call__(self, audio: torch.Tensor, lengths=None) -> AudioOut:
-        """audio [B, L] or [B, 1, L] at source_rate; lengths int [B] in mel frames (x hop = 256 samples), as
-        Generator.forward and Denoiser.forward take it; None: every row is L samples long."""
-        audio, lens = self._resampled(audio, lengths, "AudioOutput")
-        return self.finish(audio, lens)
+    def fixed_gain(self, B: int, device, gain_db=None) -> torch.Tensor:
+        """-> g fp32 [B] on `device`: limiter.fixed_gain_ref of the stage's gain_db, or of the per-row override (a
+        sequence or CPU tensor of B finite floats), converted on the host and uploaded: no host synchronisation. A
+        device tensor is refused, since reading it would force one."""
+        if self.gain_db is None:
+            raise ValueError("AudioOutput: gain_db= of a call overrides the stage's fixed gain; the stage was built "
+                             "without gain_db=")
+        if gain_db is None:
+            vals = [self.gain_db] * B
+        else:
+            if isinstance(gain_db, torch.Tensor):
+                if gain_db.device.type != "cpu":
+                    raise ValueError("AudioOutput: gain_db is a sequence or a CPU tensor (a device tensor would have "
+                                     "to be read back)")
+                gain_db = gain_db.reshape(-1).tolist()
+            vals = [float(v) for v in gain_db]
+            if len(vals) != B:
+                raise ValueError(f"AudioOutput: gain_db has {len(vals)} entries for {B} rows")
+        g = torch.tensor([float(lm.fixed_gain_ref(v)) for v in vals], dtype=torch.float32)
+        return g.to(device, non_blocking=True)
 
     @torch.inference_mode()
-    def finish(self, audio: torch.Tensor, lens_samples: torch.Tensor) -> AudioOut:
+    def __call__(self, audio: torch.Tensor, lengths=None, gain_db=None) -> AudioOut:
+        """audio [B, L] or [B, 1, L] at source_rate; lengths int [B] in mel frames (x hop = 256 samples), as
+        Generator.forward and Denoiser.forward take it; None: every row is L samples long. gain_db: per-row fixed
+        gains in dB in place of the stage's gain_db= (a sequence or CPU tensor of B finite floats)."""
+        if gain_db is not None and self.gain_db is None:
+            self.fixed_gain(0, None, gain_db)  # ValueError before any launch
+        audio, lens = self._resampled(audio, lengths, "AudioOutput")
+        return self.finish(audio, lens, gain_db)
+
+    @torch.inference_mode()
+    def finish(self, audio: torch.Tensor, lens_samples: torch.Tensor, gain_db=None) -> AudioOut:
         """The level-and-encode half of __call__: audio fp32 [B, L] already at sample_rate, lens_samples int32 [B] in
         samples. What __call__ runs after its rate conversion, and what LongForm runs on joined documents."""
+        if gain_db is not None and self.gain_db is None:
+            self.fixed_gain(0, None, gain_db)
         rt.require_gpu(audio, what="AudioOutput.finish")
         if audio.dim() != 2:
             raise ValueError(f"AudioOutput.finish: audio {tuple(audio.shape)}, expected [B, L]")
         lens = lens_samples
+        if self.gain_db is not None:
+            g = self.fixed_gain(audio.shape[0], audio.device, gain_db)
+            if self.limiter is not None:
+                y = self._limited_fixed(audio, lens, g).audio
+            else:
+                y = rt.f32c(audio) * g[:, None]  # fl32(g x), one rounded product per sample
+            out, _ = rt.encode_audio(y, lens, None, 1.0, True, self.encoding)
+            return AudioOut(out, lens, self.sample_rate, g)
         if self.limiter is not None:
             # the limited signal through the unchanged encoder: "rms" at mean square 1 and level 1 is gain 1, which
             # the limit caps at 1 / peak = ceiling / ((1 + eps) TP'): the trim
@@ -200,14 +250,29 @@ class AudioOutput:
         trim = torch.where(peak_eff > 0, 1.0 / peak_eff.double(), torch.ones_like(energy)).clamp_(max=1.0).float()
         return Limited(y, lens, self.sample_rate, gain, reduction, trim), peak_eff
 
+    def _limited_fixed(self, audio: torch.Tensor, lens: torch.Tensor, g: torch.Tensor) -> Limited:
+        """limiter.limit_fixed_ref per row: one mt_peak_envelope and one mt_limit at stats (1, 1) and level 1, which
+        make the kernel's gain g itself"""
+        plan4 = rt.resample_plan(self.sample_rate, 4 * self.sample_rate, self.zeros, self.beta, audio.device)
+        env = rt.peak_envelope(audio, lens, plan4)
+        ones = torch.ones_like(g)
+        y, gain, reduction = rt.limit(audio, env, lens, (ones, ones.double()), 1.0, 10.0 ** (self.true_peak / 20.0),
+                                      self.limiter_window, gain_in=g)
+        return Limited(y, lens, self.sample_rate, gain, reduction, ones)
+
     @torch.inference_mode()
-    def limited(self, audio: torch.Tensor, lens_samples: torch.Tensor) -> Limited:
+    def limited(self, audio: torch.Tensor, lens_samples: torch.Tensor, gain_db=None) -> Limited:
         """audio fp32 [B, L] already at sample_rate, lens_samples int32 [B] in samples (as finish takes them) -> the
-        levelled and limited rows before trim and encoding, and the report (limiter.limiter_ref per row). Needs
-        limiter=. No host synchronisation: the gains, energies and peaks stay on the device."""
+        levelled and limited rows before trim and encoding, and the report (limiter.limiter_ref per row; with
+        gain_db=, limiter.limit_fixed_ref: gain = g, trim = 1). Needs limiter=. No host synchronisation: the gains,
+        energies and peaks stay on the device."""
         if self.limiter is None:
             raise ValueError("AudioOutput.limited: the stage was built without limiter=")
+        if gain_db is not None and self.gain_db is None:
+            self.fixed_gain(0, None, gain_db)
         rt.require_gpu(audio, what="AudioOutput.limited")
         if audio.dim() != 2:
             raise ValueError(f"AudioOutput.limited: audio {tuple(audio.shape)}, expected [B, L]")
+        if self.gain_db is not None:
+            return self._limited_fixed(audio, lens_samples, self.fixed_gain(audio.shape[0], audio.device, gain_db))
         return self._limited(audio, lens_samples)[0]

@@ -31,6 +31,17 @@ uploaded once, and each step enqueues a fixed chain for the whole batch: gather 
 scatter -> gather -> mt_denoise_ragged -> scatter -> mt_resample_range -> mt_audio_encode. Not streamed: the CFM solve
 (global over the utterance) and level normalisation (`normalize="peak"` / `"rms"` and `loudness=` need the whole
 utterance).
+
+Level in a stream: an output stage with a gain fixed beforehand, `AudioOutput(..., gain_db=6.0)`, and
+with it the look-ahead limiter, `AudioOutput(..., gain_db=6.0, true_peak=-1.0, limiter=5.0)`, is streamed, again bit
+for bit the one-shot call of the same stage; `s(mel, lengths, gain_db=[...])` sets the gain row by row. Once the gain
+is known the limiter is local: the envelope of a sample reads `envelope_reach` = 10 samples ahead (the 4x filter)
+and the gain curve W - 1 envelope samples ahead (W: the limiter's window in samples). The chain of a step then ends
+... -> mt_resample_range (into a stitched buffer at the output rate) -> mt_peak_envelope_range (into a stitched
+envelope) -> mt_limit_range -> mt_audio_encode, and a chunk ends `envelope_reach + W - 1` output samples before the
+resampled range does: the added delay, 89 samples = 5.6 ms at 16 kHz with limiter=5.0 (W = 80). Without limiter= the
+gain is one fp32 product on the delivered range and nothing is delayed. `WaveStreamer.reduction` holds the deepest
+reduction of every row of the stream in progress.
 """
 from __future__ import annotations
 
@@ -38,6 +49,7 @@ from typing import Iterator, List, NamedTuple, Optional
 
 import torch
 
+from matcha_hip import limiter as lm
 from matcha_hip import runtime as rt
 from matcha_hip import stream_plan as sp
 
@@ -83,6 +95,11 @@ class WaveStreamer:
         self.hop = eng.hop
         self.reach = generator.receptive_field() if _halo is None else int(_halo)
         self.resample = output is not None and output.sample_rate != output.source_rate
+        self.fixed_gain = output is not None and getattr(output, "gain_db", None) is not None
+        self.limited = self.fixed_gain and output.limiter is not None
+        # fp32 [B] on the device: min s of every row of the stream in progress (1: the limiter never worked); valid
+        # for a row once its `done` chunk was yielded. None before the first stream and without limiter=.
+        self.reduction: Optional[torch.Tensor] = None
 
     def _factor(self, device):
         if not self.resample:
@@ -91,11 +108,23 @@ class WaveStreamer:
         p = rt.resample_plan(o.source_rate, o.sample_rate, o.zeros, o.beta, device)
         return p, p.up, p.down, p.half
 
+    def _plan4(self, device):
+        """the 4x plan of the limiter's envelope at the output rate, or None"""
+        if not self.limited:
+            return None
+        o = self.output
+        return rt.resample_plan(o.sample_rate, 4 * o.sample_rate, o.zeros, o.beta, device)
+
+    def _plan(self, lens, up, down, half, plan4) -> sp.Plan:
+        lim = {} if plan4 is None else dict(env_reach=lm.envelope_reach(plan4.half),
+                                            window=self.output.limiter_window)
+        return sp.plan(lens, self.chunk_frames, self.first_chunk_frames, up, down, half, reach=self.reach,
+                       denoise=self.denoiser is not None, hop=self.hop, **lim)
+
     def plan(self, lengths, device=None) -> sp.Plan:
         """the stream's steps for utterances of `lengths` mel frames (a sequence of ints)"""
         _, up, down, half = self._factor(device)
-        return sp.plan(lengths, self.chunk_frames, self.first_chunk_frames, up, down, half, reach=self.reach,
-                       denoise=self.denoiser is not None, hop=self.hop)
+        return self._plan(lengths, up, down, half, self._plan4(device))
 
     def schedule(self, lengths, device=None) -> List[int]:
         """e_c of every step: the chunk of step c needs the mel frames below e_c + reach, and no others"""
@@ -112,7 +141,12 @@ class WaveStreamer:
         t = torch.tensor(flat or [0], dtype=torch.int32).pin_memory().to(device, non_blocking=True)
         return [t[o:o + len(c)] for o, c in zip(offs, cols)]
 
-    def __call__(self, mel: torch.Tensor, lengths) -> Iterator[Chunk]:
+    def __call__(self, mel: torch.Tensor, lengths, gain_db=None) -> Iterator[Chunk]:
+        """gain_db: per-row fixed gains in dB in place of the output stage's gain_db= (a sequence or CPU tensor of B
+        finite floats; the stage must have been built with gain_db=)"""
+        if gain_db is not None and not self.fixed_gain:
+            raise ValueError("WaveStreamer: gain_db= overrides the output stage's fixed gain; the stage was built "
+                             "without gain_db=")
         rt.require_gpu(mel, what="WaveStreamer")
         if mel.dim() != 3 or mel.shape[1] != 80:
             raise ValueError(f"WaveStreamer: mel {tuple(mel.shape)}, expected [B, 80, T]")
@@ -124,15 +158,16 @@ class WaveStreamer:
             raise ValueError(f"lengths {tuple(lens.shape)}: expected ({B},)")
         # the one host sync of the stream
         lens = [min(max(int(v), 0), T) for v in lens.tolist()]
-        return self._run(mel, lens)
+        gain = self.output.fixed_gain(B, mel.device, gain_db) if self.fixed_gain else None  # refusals before the start
+        return self._run(mel, lens, gain)
 
-    def _run(self, mel, lens) -> Iterator[Chunk]:
+    def _run(self, mel, lens, gain=None) -> Iterator[Chunk]:
         dev = mel.device
         B, _, T = mel.shape
         hop = self.hop
         rplan, up, down, half = self._factor(dev)
-        pl = sp.plan(lens, self.chunk_frames, self.first_chunk_frames, up, down, half, reach=self.reach,
-                     denoise=self.denoiser is not None, hop=hop)
+        plan4 = self._plan4(dev)
+        pl = self._plan(lens, up, down, half, plan4)
         x = mel if (mel.dtype == torch.float32 and mel.is_contiguous()) else rt.f32c(mel)
         g = self.generator
         eng = g.engine()
@@ -162,6 +197,15 @@ class WaveStreamer:
             wav_rows = None if self.per_row else torch.empty((Rmax, 1, Wv * hop), dtype=torch.float32, device=dev)
             aud_rows = torch.empty((Rmax, Wd), dtype=torch.float32, device=dev) if self.denoiser is not None else None
             done = [tabs[16 * i + 15].bool() for i in range(len(pl.steps))]
+            if plan4 is not None:
+                # stitched buffers at the output rate: the resampled signal (the denoised buffer itself at equal
+                # rates) and its envelope; a range kernel reads only what the stage before made final
+                Lo = max(max(pl.n_out, default=0), 1)
+                out_lens = torch.tensor(pl.n_out, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+                res = torch.zeros((B, Lo), dtype=torch.float32, device=dev) if rplan is not None else den
+                envb = torch.zeros_like(res)
+                ceiling = 10.0 ** (self.output.true_peak / 20.0)
+                red = self.reduction = torch.ones((B,), dtype=torch.float32, device=dev)  # this stream's own
         enc = self.output.encoding if self.output is not None else None
         for i, st in enumerate(pl.steps):
             t = tabs[16 * i:16 * i + 16]
@@ -181,14 +225,28 @@ class WaveStreamer:
                     rt.window_gather(raw, t[6], t[7], t[8], Wd, out=aud_rows[:R])
                     y = rt.denoise(aud_rows[:R], self.denoiser.bias_spec, self.strength, lengths=t[9], hop=hop)
                     rt.window_scatter(y, t[6], t[10], t[11], t[12], den)
-                cnt = st.m_hi - st.m_lo
+                if plan4 is not None:
+                    # the resampled range into its place in the stitched buffer, its envelope, then the delivered
+                    # range through the limiter; rows that ended are clipped inside the kernels
+                    if rplan is not None and st.m_hi > st.m_lo:
+                        part, _ = rt.resample_range(den, rplan, src_lens, hop, st.m_lo, st.m_hi - st.m_lo)
+                        res[:, st.m_lo:st.m_hi] = part  # m_hi <= the greatest output count = Lo
+                    if st.p_hi > st.p_lo:
+                        rt.peak_envelope_range(res, out_lens, plan4, st.p_lo, st.p_hi - st.p_lo, envb)
+                y_lo, y_hi = st.delivered
+                cnt = y_hi - y_lo
                 if cnt == 0:
                     code = rt.ENCODING_CODES[enc][1] if enc is not None else torch.float32
                     audio = torch.empty((B, 0), dtype=code, device=dev)
+                elif plan4 is not None:
+                    audio, _ = rt.limit_range(res, envb, out_lens, gain, ceiling, self.output.limiter_window, y_lo,
+                                              cnt, red)
                 elif rplan is not None:
-                    audio, _ = rt.resample_range(den, rplan, src_lens, hop, st.m_lo, cnt)
+                    audio, _ = rt.resample_range(den, rplan, src_lens, hop, y_lo, cnt)
                 else:
-                    audio = den[:, st.m_lo:st.m_hi]
+                    audio = den[:, y_lo:y_hi]
+                if cnt and gain is not None and plan4 is None:
+                    audio = audio * gain[:, None]  # fl32(g x): one rounded fp32 product per sample
                 if cnt and self.output is not None:
                     o = self.output
                     audio, _ = rt.encode_audio(audio, t[14], None, o.level, o.limit, o.encoding)

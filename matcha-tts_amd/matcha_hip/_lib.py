@@ -109,6 +109,9 @@ SIGNATURES = {
     "mt_peak_envelope": (c_int, [P, c_int, c_int, P, P, c_int, P, P, c_size_t, P]),
     "mt_limit_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mt_limit": (c_int, [P, P, c_int, c_int, P, P, P, P, c_double, c_double, c_int, P, P, P, P, c_size_t, P]),
+    "mt_peak_envelope_range": (c_int, [P, c_int, c_int, P, P, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "mt_limit_range_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mt_limit_range": (c_int, [P, P, c_int, c_int, P, P, c_double, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
     "mt_audio_edges_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mt_audio_edges": (c_int, [P, c_int, c_int, P, c_float, c_int, P, P, P, c_size_t, P]),
     "mt_join_plan": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),

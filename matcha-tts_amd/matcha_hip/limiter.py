@@ -12,6 +12,9 @@ float32(10^(ceiling / 20)).
 * ``limiter_ref``: the make-up passes: the gain g rises until the limited signal reads the target loudness, then one
   static trim holds what the smoothing let through of the true peak, with the headroom (trim_headroom) that the fp32
   arithmetic of delivery and meter needs, so that the meter reads the delivered signal at or under the ceiling.
+* ``fixed_gain_ref`` / ``limit_fixed_ref``: the limiter at a gain fixed beforehand, in one pass, with nothing measured,
+  made up or trimmed; ``envelope_reach``: how far ahead the envelope reads. What a stream delivers chunk by chunk
+  (the ranges are stream_plan's).
 """
 from __future__ import annotations
 
@@ -105,6 +108,37 @@ def apply_ref(x, g0, s) -> np.ndarray:
     with np.errstate(invalid="ignore", over="ignore", under="ignore"):
         t = (np.float32(g0) * x).astype(np.float32)
         return (t * np.asarray(s, dtype=np.float32)).astype(np.float32)
+
+
+def envelope_reach(half4: int) -> int:
+    """The samples after i that p[i] reads, with a 4x filter of 2 half4 + 1 taps: the chain of the 4x output 4i + 3
+    starts at the sample (half4 + 4i + 3) // 4 = i + (half4 + 3) // 4 (10 for the default filter, half4 = 40)."""
+    half4 = int(half4)
+    if half4 < 0:
+        raise ValueError(f"envelope_reach: half-length {half4}")
+    return (half4 + 3) // 4
+
+
+def fixed_gain_ref(gain_db) -> np.float32:
+    """float32(10^(float64(gain_db) / 20)): a gain chosen beforehand, in dB; ValueError unless finite"""
+    gain_db = float(gain_db)
+    if not math.isfinite(gain_db):
+        raise ValueError(f"limiter: gain_db must be finite, got {gain_db}")
+    with np.errstate(over="ignore"):
+        return np.float32(10.0 ** (np.float64(gain_db) / 20.0))
+
+
+def limit_fixed_ref(x, gain_db, ceiling_dbtp: float, W: int, zeros: int = 10, beta: float = 5.0):
+    """-> (y fp32 [n], reduction): the limiter at a fixed gain g = fixed_gain_ref(gain_db), one pass: s =
+    gain_curve_ref(envelope_ref(x), g, c32, W), y = apply_ref(x, g, s), reduction = min s (1 for an empty row). No
+    loudness is measured, nothing is made up or trimmed, and there is no "levelled at all" test: a silent row is
+    g * 0. Every part of it is local (envelope_reach samples ahead for p, W - 1 more for s), so a stream can
+    deliver it chunk by chunk."""
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    g = fixed_gain_ref(gain_db)
+    c32 = np.float32(10.0 ** (float(ceiling_dbtp) / 20.0))
+    s = gain_curve_ref(envelope_ref(x, zeros, beta), g, c32, W)
+    return apply_ref(x, g, s), (s.min() if s.shape[0] else np.float32(1.0))
 
 
 def next_gain_ref(g, level: float, E) -> np.float32:

@@ -1063,6 +1063,83 @@ def limit(audio: torch.Tensor, env: torch.Tensor, lengths, stats, level: float, 
     return y, gain, reduction
 
 
+def _range_args(what: str, i_lo, cnt):
+    i_lo, cnt = int(i_lo), int(cnt)
+    if i_lo < 0 or cnt < 1 or i_lo + cnt >= (1 << 31) - 4 * LIMIT_TILE:
+        raise ValueError(f"{what}: samples [{i_lo}, {i_lo} + {cnt})")
+    return i_lo, cnt
+
+
+def _inplace_rows(what: str, name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 \
+            or (shape is not None and t.shape != shape):
+        raise ValueError(f"{what}: {name} is a contiguous fp32 [B, L] tensor" + (f" {tuple(shape)}" if shape else ""))
+    return t
+
+
+def peak_envelope_range(audio: torch.Tensor, lengths, plan4: ResamplePlan, i_lo: int, cnt: int,
+                        env: torch.Tensor) -> torch.Tensor:
+    """The samples [i_lo, i_lo + cnt) of ``peak_envelope``'s rows, written into `env` (fp32 [B, L], the same buffer
+    across calls) where they lie inside the row, bit for bit; the rest of env keeps its contents
+    (mt_peak_envelope_range). lengths: the rows' FINAL lengths in samples. Of a row it reads no sample past
+    min(len - 1, i_lo + cnt - 1 + limiter.envelope_reach(plan4.half)): the rest of `audio` may still be unwritten
+    (DESIGN.md §24). audio and env are fp32 and contiguous: read and written in place."""
+    require_gpu(audio, what="peak_envelope_range")
+    if (plan4.up, plan4.down) != (4, 1):
+        raise ValueError(f"peak_envelope_range: the plan is {plan4.up}/{plan4.down}; the envelope is taken at 4/1")
+    _inplace_rows("peak_envelope_range", "audio", audio)
+    _inplace_rows("peak_envelope_range", "env", env, audio.shape)
+    require_gpu(env, what="peak_envelope_range")
+    i_lo, cnt = _range_args("peak_envelope_range", i_lo, cnt)
+    B, L = audio.shape
+    lens = _lens32(lengths, B, audio.device)
+    L_ = lib()
+    taps = plan4.taps if plan4.taps.device == audio.device else plan4.taps.to(audio.device)
+    ws = _Workspace.get(L_.mt_peak_envelope_workspace_bytes(), audio.device)
+    check(L_.mt_peak_envelope_range(ptr(audio), B, L, ptr(lens), ptr(taps), plan4.half, i_lo, cnt, ptr(env),
+                                    ws.data_ptr(), ws.numel(), stream_handle(audio.device)), "peak_envelope_range")
+    return env
+
+
+def limit_range(audio: torch.Tensor, env: torch.Tensor, lengths, gain: torch.Tensor, ceiling: float, W: int,
+                i_lo: int, cnt: int, reduction: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The samples [i_lo, i_lo + cnt) of the limiter at a fixed gain -> (out fp32 [B, cnt], out_cnt int32 [B]): the
+    bits of ``limit(audio, env, lengths, (ones, ones), 1.0, ceiling, W, gain_in=gain)``'s columns, i.e. of
+    limiter.apply_ref(x, gain, limiter.gain_curve_ref(env, gain, float32(ceiling), W)), zero past a row's end
+    (mt_limit_range). gain: fp32 [B] on the device, used as it is. Of env it reads [i_lo - (W - 1), i_lo + cnt + W -
+    2] inside the row, of audio the range: the rest of both may still be unwritten. reduction (fp32 [B], device) is
+    updated in place to min(reduction, min s over the range); start it at 1."""
+    require_gpu(audio, what="limit_range")
+    ceiling, W = float(ceiling), int(W)
+    if not (0.0 < ceiling < float("inf")):
+        raise ValueError(f"limit_range: ceiling {ceiling} must be finite and positive")
+    if not 1 <= W <= LIMIT_MAX_WINDOW:
+        raise ValueError(f"limit_range: window of {W} samples outside 1 .. {LIMIT_MAX_WINDOW}")
+    _inplace_rows("limit_range", "audio", audio)
+    _inplace_rows("limit_range", "env", env, audio.shape)
+    i_lo, cnt = _range_args("limit_range", i_lo, cnt)
+    B, L = audio.shape
+    dev = audio.device
+    for name, t in (("gain", gain), ("reduction", reduction)):
+        if not isinstance(t, torch.Tensor) or t.shape != (B,) or t.dtype != torch.float32 or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"limit_range: {name} is a contiguous fp32 [{B}] tensor on {dev}")
+    if env.device != dev:
+        raise ValueError(f"limit_range: env is on {env.device}, audio on {dev}")
+    lens = _lens32(lengths, B, dev)
+    if out is None:
+        out = torch.empty((B, cnt), dtype=torch.float32, device=dev)
+    elif out.shape != (B, cnt) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"limit_range: out {tuple(out.shape)}: expected contiguous fp32 ({B}, {cnt}) on {dev}")
+    out_cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    L_ = lib()
+    ws = _Workspace.get(L_.mt_limit_range_workspace_bytes(B, cnt, W), dev)
+    check(L_.mt_limit_range(ptr(audio), ptr(env), B, L, ptr(lens), ptr(gain), ceiling, W, i_lo, cnt, ptr(out),
+                            ptr(out_cnt), ptr(reduction), ws.data_ptr(), ws.numel(), stream_handle(dev)),
+          "limit_range")
+    return out, out_cnt
+
+
 def resample_range(audio: torch.Tensor, plan: ResamplePlan, lengths, lmul: int, m_lo: int, cnt: int,
                    out: Optional[torch.Tensor] = None):
     """The outputs [m_lo, m_lo + cnt) of ``resample``'s rows -> (out fp32 [B, cnt], out_cnt int32 [B]), bit for bit,

@@ -13,6 +13,8 @@ the one-shot call: the concatenated chunks of a row are, bit for bit, that row o
 * ``denoise_reach()`` / ``denoise_window`` / ``denoise_final``: the STFT denoiser's window rule. The kernel
   transforms the frames (2j, 2j + 1) as one complex FFT, so a window starts on an even frame of the utterance and a
   sample is kept only when every frame covering it, and each such frame's partner, lies wholly inside the window.
+* ``envelope_final`` / ``limit_final``: what of the limiter's envelope and of its output is final once so much of the
+  stage before is (a fixed gain and the limiter in a stream).
 * ``plan(lengths, chunk_frames, ...)``: per step and live row the vocoder window and crop, the denoise window and
   crop, and the output-sample range that becomes final.
 
@@ -188,6 +190,30 @@ def resample_last_read(m_hi: int, up: int, down: int, half: int) -> int:
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# fixed gain and limiter (matcha_hip/limiter.py is the specification of the two stages)
+# ---------------------------------------------------------------------------------------------------------------
+
+def envelope_final(avail: int, n: int, ereach: int) -> int:
+    """Envelope samples [0, result) of a row of n samples that are final once its first `avail` samples are: all n
+    when avail >= n; else p[i] reads the samples up to i + ereach (limiter.envelope_reach), so it needs
+    i + ereach < avail."""
+    avail, n = int(avail), int(n)
+    if avail >= n:
+        return n
+    return max(0, avail - int(ereach))
+
+
+def limit_final(avail_env: int, n: int, W: int) -> int:
+    """Limited samples [0, result) of a row of n samples that are final once its first `avail_env` envelope samples
+    are: all n when avail_env >= n; else s[i] reads the envelope up to i + W - 1 (the last of the W windows that
+    hold i), so it needs i + W - 1 < avail_env."""
+    avail_env, n = int(avail_env), int(n)
+    if avail_env >= n:
+        return n
+    return max(0, avail_env - (int(W) - 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # the plan
 # ---------------------------------------------------------------------------------------------------------------
 
@@ -224,15 +250,26 @@ class Step:
     raw_final: List[int]   # per row, after this step: frames of final vocoder output,
     den_final: List[int]   # frames of final denoised audio (= raw_final without a denoiser),
     out_final: List[int]   # final outputs
+    # with a limiter (plan(env_reach=, window=)): [m_lo, m_hi) is the resampled range made final, not yet delivered;
+    p_lo: Optional[int] = None   # the envelope samples [p_lo, p_hi) become final,
+    p_hi: Optional[int] = None
+    y_lo: Optional[int] = None   # and the limited samples [y_lo, y_hi) are delivered (each clipped to the row's count)
+    y_hi: Optional[int] = None
+
+    @property
+    def delivered(self):
+        """the range of outputs [lo, hi) this step delivers: [y_lo, y_hi) with a limiter, else [m_lo, m_hi)"""
+        return (self.m_lo, self.m_hi) if self.y_hi is None else (self.y_lo, self.y_hi)
 
     def out_counts(self, n_out):
         """per row: (offset, valid samples, done) of the chunk this step delivers; done in the one step that
         delivers the row's last sample (the first step for an empty row)"""
         res = []
+        lo, hi = self.delivered
         for n in n_out:
-            off = min(self.m_lo, n)
-            cnt = min(max(n - self.m_lo, 0), self.m_hi - self.m_lo)
-            res.append((off, cnt, n <= self.m_hi and (cnt > 0 or (n == 0 and self.index == 0))))
+            off = min(lo, n)
+            cnt = min(max(n - lo, 0), hi - lo)
+            res.append((off, cnt, n <= hi and (cnt > 0 or (n == 0 and self.index == 0))))
         return res
 
 
@@ -248,6 +285,8 @@ class Plan:
     half: int
     n_out: List[int]
     steps: List[Step]
+    env_reach: Optional[int] = None
+    window: Optional[int] = None
 
     @property
     def max_vocoder_window(self) -> int:
@@ -259,11 +298,12 @@ class Plan:
 
     @property
     def max_chunk(self) -> int:
-        return max(st.m_hi - st.m_lo for st in self.steps)
+        return max(st.delivered[1] - st.delivered[0] for st in self.steps)
 
 
 def plan(lengths, chunk_frames: int, first_chunk_frames: Optional[int] = None, up: int = 1, down: int = 1,
-         half: int = 0, *, reach: int, denoise: bool = True, hop: int = HOP) -> Plan:
+         half: int = 0, *, reach: int, denoise: bool = True, hop: int = HOP, env_reach: Optional[int] = None,
+         window: Optional[int] = None) -> Plan:
     """The steps of a stream over a batch of utterances of `lengths` mel frames.
 
     The mel-frame schedule [s_c, e_c) is shared by the batch: e_0 = first_chunk_frames (default chunk_frames),
@@ -290,11 +330,18 @@ def plan(lengths, chunk_frames: int, first_chunk_frames: Optional[int] = None, u
         raise ValueError(f"plan: chunk_frames {chunk} / first_chunk_frames {first} must be >= 1")
     if up < 1 or down < 1 or half < 0 or reach < 0 or math.gcd(up, down) != 1:
         raise ValueError(f"plan: factor {up}/{down} (coprime, positive), half {half}, reach {reach}")
+    if (env_reach is None) != (window is None):
+        raise ValueError("plan: env_reach and window come together (a limiter after the rate change) or not at all")
+    limited = window is not None
+    if limited:
+        env_reach, window = int(env_reach), int(window)
+        if env_reach < 0 or window < 1:
+            raise ValueError(f"plan: env_reach {env_reach} (>= 0), window {window} (>= 1)")
     B = len(lens)
     n_out = [out_length(hop * n, up, down) for n in lens]
     V, D, M = [0] * B, [0] * B, [0] * B
     steps: List[Step] = []
-    s, e, m_done = 0, first, 0
+    s, e, m_done, p_done, y_done = 0, first, 0, 0, 0
     while True:
         voc, den = Windows(), (Windows() if denoise else None)
         for b, n in enumerate(lens):
@@ -317,9 +364,16 @@ def plan(lengths, chunk_frames: int, first_chunk_frames: Optional[int] = None, u
             M[b] = resample_final(hop * D[b], hop * n, up, down, half)
         open_rows = [M[b] for b in range(B) if D[b] < lens[b]]
         m_hi = max(min(open_rows) if open_rows else max(n_out, default=0), m_done)
-        steps.append(Step(len(steps), s, e, voc, den, m_done, m_hi, list(V), list(D), list(M)))
+        step = Step(len(steps), s, e, voc, den, m_done, m_hi, list(V), list(D), list(M))
+        if limited:
+            # an open row goes on past m_hi: envelope_final / limit_final of a row that has not ended
+            p_hi = max(m_hi - env_reach, p_done) if open_rows else m_hi
+            y_hi = max(p_hi - (window - 1), y_done) if open_rows else m_hi
+            step.p_lo, step.p_hi, step.y_lo, step.y_hi = p_done, p_hi, y_done, y_hi
+            p_done, y_done = p_hi, y_hi
+        steps.append(step)
         m_done = m_hi
         if not open_rows:
             break
         s, e = e, e + chunk
-    return Plan(lens, chunk, first, reach, bool(denoise), up, down, half, n_out, steps)
+    return Plan(lens, chunk, first, reach, bool(denoise), up, down, half, n_out, steps, env_reach, window)

@@ -12,6 +12,10 @@ launch work where the GPU waits for it. Warm-up runs of both paths first, then `
 measurements; medians and the spread (min, max) are reported. The stream's result is compared with the one-shot's
 bit for bit once per shape. Prints one JSON line per shape and writes them all to --out. Not part of the test suite.
 
+Level in the stream: `--gain-db G` gives the output stage a fixed gain, `--limiter MS` with it the
+look-ahead limiter at -1 dBTP (the one-shot path then runs the same stage); written to
+profiles/stream_latency_limiter.json with `--out`. The chunks end `added_delay_samples` earlier than without.
+
 Launches per step: `rocprofv3 --kernel-trace --stats ... -- python tools/stream_latency.py --trace-streams K` for two
 values of K; the difference of the two call counts belongs to the streams alone (tools/stream_launches.py).
 """
@@ -53,6 +57,8 @@ def main():
     p.add_argument("--first", type=int, default=8)
     p.add_argument("--rate", type=int, default=16000)
     p.add_argument("--shapes", default="1x728,32x728")
+    p.add_argument("--gain-db", type=float, default=None, help="a fixed gain in dB for the output stage")
+    p.add_argument("--limiter", type=float, default=None, help="with --gain-db: the limiter's window in ms")
     p.add_argument("--trace-streams", type=int, default=0,
                    help="run only this many streams of the first shape, untimed, and exit: for a kernel trace (two "
                         "runs with different counts; their difference is the launches of the streams alone)")
@@ -65,7 +71,9 @@ def main():
     dev = torch.device("cuda", 0)
     g = _generator(dev)
     den = Denoiser(g, mode="zeros")
-    out = AudioOutput(a.rate, encoding="pcm16")
+    if a.limiter is not None and a.gain_db is None:
+        raise SystemExit("stream_latency: --limiter needs --gain-db")
+    out = AudioOutput(a.rate, encoding="pcm16", gain_db=a.gain_db, true_peak=-1.0, limiter=a.limiter)
     s = WaveStreamer(g, den, out, chunk_frames=a.chunk, first_chunk_frames=a.first, strength=0.00025)
     ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
     results = []
@@ -119,13 +127,17 @@ def main():
             t_first.append(f)
             t_last.append(l)
         pl = s.plan(host_lens, dev)
-        first_step = next(st for st in pl.steps if st.m_hi > st.m_lo)
+        first_step = next(st for st in pl.steps if st.delivered[1] > st.delivered[0])
+        delay = 0 if pl.window is None else pl.env_reach + pl.window - 1
         r = {"B": B, "T": T, "chunk_frames": a.chunk, "first_chunk_frames": a.first, "rate": a.rate,
-             "encoding": "pcm16", "repeats": a.repeats, "warmup": a.warmup, "steps": steps,
-             "first_chunk_step": first_step.index, "first_chunk_samples": first_step.m_hi - first_step.m_lo,
+             "encoding": "pcm16", "gain_db": a.gain_db, "limiter_ms": a.limiter, "added_delay_samples": delay,
+             "repeats": a.repeats, "warmup": a.warmup, "steps": steps,
+             "first_chunk_step": first_step.index,
+             "first_chunk_samples": first_step.delivered[1] - first_step.delivered[0],
              "first_window_frames": max(first_step.voc.length), "max_window_frames": pl.max_vocoder_window,
              "vocoder_frames_streamed": sum(sum(st.voc.length) for st in pl.steps) // B,
              "bit_identical_to_one_shot": same,
+             "min_reduction": None if s.reduction is None else round(float(s.reduction.min()), 6),
              "one_shot": _stats(t_one), "stream_first_chunk": _stats(t_first), "stream_last_chunk": _stats(t_last)}
         print(json.dumps(r), flush=True)
         results.append(r)
