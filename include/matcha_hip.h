@@ -27,6 +27,8 @@
  *   mt_limit_range                  mt_limit's rows, read in place from buffers that are still being filled
  *   mt_audio_edges, mt_join_plan, <- long-form synthesis: a batch of sentences joined into documents (trim, pauses,
  *   mt_join                         crossfades); no counterpart in the reference, which writes one file per sentence
+ *   mt_audio_decode,             <- the recording input stage: PCM / mu-law bytes of a ragged batch to the log-mel that
+ *   mt_log_mel_ragged               align, edit and the trainer take (the reference featurizes one file per CPU worker)
  *   mt_maximum_path              <- train_standalone.maximum_path train_standalone.py:280-325 (MAS)
  *   mt_durations_tokens, mt_align   duration control and a forced aligner for inference: no counterpart in the
  *                                   reference (its log-prior train_standalone.py:639-644 in direct form, textbook MAS)
@@ -534,6 +536,38 @@ int mt_join(const float* seg, int S, int L, const int32_t* start, const int32_t*
  * ------------------------------------------------------------------------------------- */
 int mt_log_mel(const float* audio, int B, int L, const float* mel_basis, float mel_mean, float mel_std, float* mel,
                void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Recording input stage (matcha_hip/audio_in.py is the specification on the CPU): the mirror image of
+ * the audio output stage, from the bytes of a ragged batch of recordings to (mel, mel_lengths) as MatchaTTS.align,
+ * MatchaTTS.edit and the trainer take them: mt_audio_decode -> mt_resample (to 22,050 Hz) -> mt_audio_stats (peak
+ * level) -> mt_audio_edges (trim) -> mt_log_mel_ragged. 1 <= B <= 65535. Neither entry point allocates on the device
+ * or uses atomics; every argument error is refused before any launch; the tables (lens, start, end) are int32 in
+ * device memory, the host cannot check them, and an entry that points outside its buffer is clamped inside the
+ * kernel: wrong audio, never an access out of range. A row's results depend on its own valid samples alone, bit for
+ * bit.
+ * ------------------------------------------------------------------------------------- */
+/* Interleaved frames -> mono fp32. raw: [B][Lcap channels] of the encoding's type (MT_ENC_F32 float, MT_ENC_PCM16
+ * int16, MT_ENC_MULAW uint8), frame i of row b at raw[b][i channels + c]; 1 <= channels <= 8, Lcap >= 1, Lcap channels
+ * < 2^31. len_b = lens[b] in frames (int32 [B], device, clamped to [0, Lcap]; NULL: Lcap). Per sample, in fp32:
+ * MT_ENC_PCM16 q / 32768 (exact); MT_ENC_MULAW the G.711 expansion of the byte (the centre of its interval, an int16)
+ * / 32768; MT_ENC_F32 the value itself, 0.0f in place of a NaN or an infinity. channels > 1: the fp32 sum in channel
+ * order ((c0 + c1) + c2) ..., then one fp32 product with float(1.0 / channels). out: fp32 [B][Lcap], written whole,
+ * 0.0f from len_b on; nothing of raw at or past frame len_b is read. out must not overlap raw. */
+int mt_audio_decode(const void* raw, int B, int Lcap, const int32_t* lens, int encoding, int channels, float* out,
+                    void* stream);
+/* mt_log_mel of every row at its own edges and gain. a_b = clamp(start[b], 0, L), e_b = clamp(end[b], a_b, L), n_b =
+ * e_b - a_b (start, end: int32 [B], device; start NULL: 0, end NULL: L). Row b's signal is s_b[i] = fl32(gain[b]
+ * audio[b][a_b + i]), i < n_b (gain fp32 [B], device; NULL: the samples as they stand), reflected at ITS two ends 0 and
+ * n_b - 1. frames[b] (int32 [B]) = 0 for n_b <= 384, else (n_b - 256) / 256 + 1. mel: fp32 [B][80][Fcap], written
+ * whole: for f < frames[b] the bits mt_log_mel gives for s_b held alone in a [1][n_b] buffer (the same frame body:
+ * FFT, magnitude, (p0 + p1) + p2 of the three thirds of each 513-bin dot product), `fill` for f >= frames[b]. Nothing
+ * of audio[b] outside [a_b, e_b) is read. Fcap >= the frame count of a row of L samples; L >= 1, L < 2^30; mel_std
+ * != 0. One workgroup per (row, 8 frames): the twiddle table is built once per workgroup and a workgroup past the
+ * row's last frame only writes `fill`. */
+int mt_log_mel_ragged(const float* audio, int B, int L, const int32_t* start, const int32_t* end, const float* gain,
+                      const float* mel_basis, float mel_mean, float mel_std, float fill, float* mel, int Fcap,
+                      int32_t* frames, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training-side (§8f rank 3): Monotonic Alignment Search, replacing train_standalone.py:280-325

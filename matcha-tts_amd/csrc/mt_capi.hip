@@ -68,6 +68,12 @@ int join_plan(const int* doc_first, int D, const int* start, const int* end, con
               int tail, int Lcap, int* dst, int* doc_len, int* bad, hipStream_t st);
 int join(const float* seg, int S, int L, const int* start, const int* end, const int* doc_first, int D, const int* dst,
          const int* doc_len, const float* ramp, int fade, float* out, int Ld, hipStream_t st);
+// mt_audio_in.hip
+int audio_decode(const void* raw, int B, int Lcap, const int* lens, int encoding, int channels, float* out,
+                 hipStream_t st);
+int log_mel_ragged(const float* audio, int B, int L, const int* start, const int* end, const float* gain,
+                   const float* basis, float mean, float stdv, float fill, float* mel, int Fcap, int* frames,
+                   hipStream_t st);
 }  // namespace mt
 
 struct mt_encoder {
@@ -564,6 +570,18 @@ int mt_log_mel(const float* audio, int B, int L, const float* mel_basis, float m
                void* stream) {
   MT_REQUIRE(audio && mel_basis && mel, "log_mel: null argument");
   return mt::log_mel(audio, B, L, mel_basis, mel_mean, mel_std, mel, (hipStream_t)stream);
+}
+
+// ---- recording input stage ----
+int mt_audio_decode(const void* raw, int B, int Lcap, const int32_t* lens, int encoding, int channels, float* out,
+                    void* stream) {
+  return mt::audio_decode(raw, B, Lcap, lens, encoding, channels, out, (hipStream_t)stream);
+}
+int mt_log_mel_ragged(const float* audio, int B, int L, const int32_t* start, const int32_t* end, const float* gain,
+                      const float* mel_basis, float mel_mean, float mel_std, float fill, float* mel, int Fcap,
+                      int32_t* frames, void* stream) {
+  return mt::log_mel_ragged(audio, B, L, start, end, gain, mel_basis, mel_mean, mel_std, fill, mel, Fcap, frames,
+                            (hipStream_t)stream);
 }
 
 // ---- op level ----

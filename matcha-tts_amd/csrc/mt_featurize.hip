@@ -10,52 +10,23 @@
 // into LDS, a radix-2 1024-point complex FFT runs in place (twiddles from sincospif, the denoiser's
 // fft1024), the 513 one-sided magnitudes stay in LDS and each of the 80 filters is a 513-long dot product
 // split over 3 lanes. Output [B][80][F] fp32, F = (L - 256) / 256 + 1 frames (torch's framing).
-#include <math.h>
-
-#include "mt_fft.h"
+#include "mt_logmel.h"  // the frame body, shared with mt_log_mel_ragged (mt_audio_in.hip)
 
 namespace mt {
 
 namespace {
-constexpr int NFFT = 1024, HOP = 256, NBIN = NFFT / 2 + 1, PAD = (NFFT - HOP) / 2, NMEL = 80;
+constexpr int NFFT = LM_NFFT, HOP = LM_HOP, PAD = LM_PAD, NMEL = LM_NMEL;
 }
 
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ audio, int L, int nfr,
                                                      const float* __restrict__ basis, float mean, float stdv,
                                                      float* __restrict__ out) {
-  __shared__ float re[NFFT], im[NFFT], twc[NFFT / 2], tws[NFFT / 2], mag[NBIN], part[3][NMEL];
-  const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  __shared__ LogMelLds s;
+  const int f = blockIdx.x, b = blockIdx.y;
   const float* x = audio + (size_t)b * L;
-  for (int k = tid; k < NFFT / 2; k += 256) {
-    float s, c;
-    sincospif(2.f * (float)k / (float)NFFT, &s, &c);
-    twc[k] = c;
-    tws[k] = s;
-  }
-  for (int n = tid; n < NFFT; n += 256) {
-    int i = f * HOP + n - PAD;  // index into the unpadded audio, reflected at both ends
-    if (i < 0) i = -i;
-    if (i >= L) i = 2 * (L - 1) - i;
-    const int r = __brev((unsigned)n) >> (32 - 10);
-    re[r] = x[i] * hann(n);
-    im[r] = 0.f;
-  }
-  fft1024(re, im, twc, tws, -1.f);
-  for (int k = tid; k < NBIN; k += 256) mag[k] = sqrtf(re[k] * re[k] + im[k] * im[k] + 1e-9f);
-  __syncthreads();
-  if (tid < 3 * NMEL) {  // filter m = tid % 80, bins of third tid / 80
-    const int m = tid % NMEL, third = tid / NMEL;
-    const int k0 = third * 171, k1 = min(NBIN, k0 + 171);
-    const float* w = basis + (size_t)m * NBIN;
-    float s = 0.f;
-    for (int k = k0; k < k1; ++k) s = fmaf(w[k], mag[k], s);
-    part[third][m] = s;
-  }
-  __syncthreads();
-  if (tid < NMEL) {
-    const float s = (part[0][tid] + part[1][tid]) + part[2][tid];
-    out[((size_t)b * NMEL + tid) * nfr + f] = (logf(fmaxf(s, 1e-5f)) - mean) / stdv;
-  }
+  logmel_twiddles(s);
+  logmel_frame(s, f, L, [x](int i) { return x[i]; }, basis, mean, stdv,
+               [=](int m, float v) { out[((size_t)b * NMEL + m) * nfr + f] = v; });
 }
 
 int log_mel(const float* audio, int B, int L, const float* basis, float mean, float stdv, float* mel, hipStream_t st) {

@@ -118,11 +118,24 @@ def librosa_mel_fn(sr, n_fft, n_mels=128, fmin=0.0, fmax=None):
 _BASIS = {}
 
 
+def mel_basis(sampling_rate, n_fft, num_mels, fmin, fmax, device) -> torch.Tensor:
+    """librosa_mel_fn on `device`, cached per configuration and device"""
+    key = (sampling_rate, n_fft, num_mels, float(fmin), float(fmax), str(device))
+    basis = _BASIS.get(key)
+    if basis is None:
+        basis = torch.from_numpy(librosa_mel_fn(sampling_rate, n_fft, num_mels, fmin, fmax)).to(device)
+        _BASIS[key] = basis
+    return basis
+
+
 def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, center=False,
-                    mel_mean=0.0, mel_std=1.0):
+                    mel_mean=0.0, mel_std=1.0, lengths=None):
     """train_standalone.py:164-201 on the GPU: y [B, L] (or [L]) fp32 in [-1, 1] -> log-mel [B, num_mels, F],
     F = (L - 256) // 256 + 1; with mel_mean / mel_std also `normalize` (train_standalone.py:204-210), fused.
-    Built for the reference's configuration (n_fft = win = 1024, hop = 256, 80 mels, center=False)."""
+    Built for the reference's configuration (n_fft = win = 1024, hop = 256, 80 mels, center=False).
+    lengths (int [B] in samples, or None): a padded batch, row b featurized as the utterance y[b, :lengths[b]] alone
+    and reflected at ITS end (mt_log_mel_ragged): frames (lengths[b] - 256) // 256 + 1 (none for 384 samples or
+    fewer) with the bits of the call on that row alone, 0 after them. Without it the rows are reflected at L."""
     if (n_fft, win_size, hop_size, num_mels, bool(center)) != (1024, 1024, 256, 80, False):
         raise NotImplementedError("the HIP featurizer is built for n_fft=win=1024, hop=256, 80 mels, center=False "
                                   "(train_standalone.py:819-827)")
@@ -132,16 +145,18 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     y = y.reshape(1, -1) if squeeze else y.reshape(y.shape[0], -1)
     y = y.contiguous()
     B, L = y.shape
+    if lengths is not None:
+        from matcha_hip.runtime import log_mel_ragged
+        if L == 0:
+            raise ValueError("mel_spectrogram: empty audio")
+        out, _ = log_mel_ragged(y, mel_basis(sampling_rate, n_fft, num_mels, fmin, fmax, y.device), None, lengths,
+                                None, mel_mean, mel_std, 0.0)
+        return out[0] if squeeze else out
     if L <= 384:
         raise ValueError(f"mel_spectrogram: {L} samples; reflect padding needs more than 384")
-    key = (sampling_rate, n_fft, num_mels, float(fmin), float(fmax), str(y.device))
-    basis = _BASIS.get(key)
-    if basis is None:
-        basis = torch.from_numpy(librosa_mel_fn(sampling_rate, n_fft, num_mels, fmin, fmax)).to(y.device)
-        _BASIS[key] = basis
+    basis = mel_basis(sampling_rate, n_fft, num_mels, fmin, fmax, y.device)
     F = (L - 256) // 256 + 1
     out = torch.empty((B, num_mels, F), dtype=torch.float32, device=y.device)
     check(lib().mt_log_mel(y.data_ptr(), B, L, basis.data_ptr(), float(mel_mean), float(mel_std), out.data_ptr(),
                            stream_handle(y.device)), "log_mel")
     return out[0] if squeeze else out
-

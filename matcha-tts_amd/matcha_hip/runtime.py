@@ -947,6 +947,70 @@ def encode_audio(audio: torch.Tensor, lengths=None, normalize=None, level=None, 
     return out, gain
 
 
+# ---- recording input stage (audio_in.py is the specification) ----------------------------------
+
+# frames per workgroup of logmel_ragged_kernel (mt_audio_in.hip LMR_FPW): tests put row ends around its multiples
+LOGMEL_FRAMES = 8
+
+
+def decode_audio(raw: torch.Tensor, lengths=None, encoding: str = "f32", channels: int = 1) -> torch.Tensor:
+    """raw [B, Lcap * channels] interleaved frames of the encoding's dtype (float32 / int16 / uint8), lengths in
+    frames (int [B], or None = Lcap) -> mono fp32 [B, Lcap]: audio_in.decode_ref of every row, zero from its length
+    on (mt_audio_decode). Nothing of raw at or past a row's length is read."""
+    require_gpu(raw, what="decode_audio")
+    if encoding not in ENCODING_CODES:
+        raise ValueError(f"encoding must be one of {list(ENCODING_CODES)}, got {encoding!r}")
+    channels = int(channels)
+    if not 1 <= channels <= 8:
+        raise ValueError(f"channels must be in 1..8, got {channels}")
+    code, dtype = ENCODING_CODES[encoding]
+    if raw.dtype != dtype:
+        raise ValueError(f"decode_audio: {encoding} frames are {dtype}, got {raw.dtype}")
+    if raw.dim() != 2 or raw.shape[1] == 0 or raw.shape[1] % channels:
+        raise ValueError(f"decode_audio: raw {tuple(raw.shape)}, expected [B, Lcap * {channels}] with Lcap >= 1")
+    raw = raw.contiguous()
+    B, Lcap = raw.shape[0], raw.shape[1] // channels
+    lens = _lens32(lengths, B, raw.device)
+    out = torch.empty((B, Lcap), dtype=torch.float32, device=raw.device)
+    check(lib().mt_audio_decode(ptr(raw), B, Lcap, ptr(lens), code, channels, ptr(out), stream_handle(raw.device)),
+          "audio_decode")
+    return out
+
+
+def log_mel_ragged(audio: torch.Tensor, basis: torch.Tensor, start=None, end=None, gain=None, mel_mean: float = 0.0,
+                   mel_std: float = 1.0, fill: float = 0.0, Fcap: Optional[int] = None):
+    """audio [B, L]; start / end int [B] in samples (None: 0 / L), gain fp32 [B] (None: 1); basis fp32 [80, 513] ->
+    (mel fp32 [B, 80, Fcap], frames int32 [B]): row b's frames are mt_log_mel's bits for fl32(gain[b] audio[b][start[b]
+    : end[b]]) held alone, reflected at its own ends; `fill` from frames[b] on (mt_log_mel_ragged). Fcap defaults to
+    the frame count of a row of L samples. audio is read in place when it is contiguous fp32; nothing comes back to
+    the host."""
+    from . import audio_in
+    require_gpu(audio, basis, what="log_mel_ragged")
+    audio = f32c(audio)
+    if audio.dim() != 2:
+        raise ValueError(f"log_mel_ragged: audio {tuple(audio.shape)}, expected [B, L]")
+    B, L = audio.shape
+    if tuple(basis.shape) != (80, 513) or basis.dtype != torch.float32:
+        raise ValueError(f"log_mel_ragged: basis {tuple(basis.shape)} {basis.dtype}, expected fp32 [80, 513]")
+    if float(mel_std) == 0.0:
+        raise ValueError("log_mel_ragged: mel_std must be non-zero")
+    need = audio_in.frames_ref(L)
+    Fcap = need if Fcap is None else int(Fcap)
+    if Fcap < need:
+        raise ValueError(f"log_mel_ragged: Fcap {Fcap} < {need}, the frames of a row of {L} samples")
+    start, end = _lens32(start, B, audio.device), _lens32(end, B, audio.device)
+    if gain is not None:
+        gain = f32c(gain.to(audio.device))
+        if gain.shape != (B,):
+            raise ValueError(f"gain {tuple(gain.shape)}: expected ({B},)")
+    mel = torch.empty((B, 80, Fcap), dtype=torch.float32, device=audio.device)
+    frames = torch.empty((B,), dtype=torch.int32, device=audio.device)
+    check(lib().mt_log_mel_ragged(ptr(audio), B, L, ptr(start), ptr(end), ptr(gain), ptr(basis.contiguous()),
+                                  float(mel_mean), float(mel_std), float(fill), ptr(mel) if Fcap else None, Fcap,
+                                  ptr(frames), stream_handle(audio.device)), "log_mel_ragged")
+    return mel, frames
+
+
 # ---- loudness and true peak (DESIGN.md §21; loudness.py is the specification) ---------------------------------
 
 # samples per chunk and per tile of the K-weighting scan (mt_loudness.hip KW_CH, KW_TILE): tests put row ends around
